@@ -8,10 +8,16 @@ architecture (no checkpoint is available offline) and inputs already resident in
 scaling: each rank runs its own pairs).
 
 The timed mode is the one that meets the north-star parity bar (<= 1e-3 max-norm on the Gaussian fields against the fp32 oracle):
-precision "bf16x3" = fp32 activations, bf16 MFMA with the hi/lo operand split (3 passes).  The plain-bf16 mode (bf16 operands,
-~2e-2 .. 1e-1 on the fields, tests/test_model_gpu.py) is timed the same way right after and reported as `second_mode`.
+precision "bf16x3" = fp32 activations, bf16 MFMA with the hi/lo operand split (3 passes).
+
+A plain run sets up, warms up, times `--steps` steps and prints the line.  Everything else it measures runs only with `--full`: the
+plain-bf16 mode (bf16 operands, ~2e-2 .. 1e-1 on the fields, tests/test_model_gpu.py) timed the same way right after and reported as
+`second_mode`, the `roofline` object of the dominant kernel, the render legs and the CPU baselines (the `--no-*` options drop single
+ones of them).  `--dump-outputs DIR` writes what the timed path returned in its last step as DIR/<name>.npy (float32 / float64;
+arrays above the size budget as a fixed, seeded sample; DIR/manifest.json says which), for comparing two builds output for output.
 
     python bench.py --gpus 1 --steps 10 --warmup 3
+    python bench.py --gpus 1 --steps 10 --warmup 3 --full
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 """
@@ -121,21 +127,83 @@ def _board_id() -> str:
         return "unknown"
 
 
+DUMP_BYTES = 60 << 20  # --dump-outputs writes at most this much (the limit is 64 MB)
+
+
+def dump_outputs(out, directory):
+    """What the timed path returned in its last step, (gaussians, segmentation output, seg masks, segments_info, query scores), as
+    DIR/<name>.npy: floating tensors as float32 (float64 stays float64), integer / bool tensors and the segment lists as float64.
+    Every array keeps at most `cap` elements: larger ones are a sample at sorted indices drawn from a generator seeded with the crc32 of
+    the name (the same indices in every run of the same shapes).  cap starts at 2^21 and halves until the whole dump fits DUMP_BYTES."""
+    import zlib
+    import numpy as np
+
+    gauss, seg, masks, infos = out[:4]
+    qs = out[4] if len(out) > 4 else None
+    arrays = []  # (name, tensor or numpy array)
+    for k, v in vars(gauss).items():
+        if torch.is_tensor(v):
+            arrays.append((f"gaussians_{k}", v))
+        elif isinstance(v, (list, tuple)) and v and all(torch.is_tensor(t) for t in v):
+            arrays += [(f"gaussians_{k}_{b}", t) for b, t in enumerate(v)]
+    arrays += [(f"seg_{k}", v) for k, v in seg.items() if torch.is_tensor(v) and not k.startswith("_")]
+    arrays += [(f"seg_masks_{b}", m) for b, m in enumerate(masks) if torch.is_tensor(m)]
+    arrays += [(f"segments_{b}", np.array([[s["id"], s["label_id"], float(s["was_fused"]), s["score"]] for s in segs], dtype=np.float64).reshape(-1, 4))
+               for b, segs in enumerate(infos)]
+    if qs is not None:
+        arrays += [(f"query_scores_{b}", q.detach().double().reshape(-1) if torch.is_tensor(q) else np.asarray(q, dtype=np.float64).reshape(-1))
+                   for b, q in enumerate(qs)]
+
+    def itemsize(v):
+        is_f32 = (v.is_floating_point() and v.dtype != torch.float64) if torch.is_tensor(v) else v.dtype == np.float32
+        return 4 if is_f32 else 8
+
+    numel = lambda v: v.numel() if torch.is_tensor(v) else v.size
+    cap = 1 << 21
+    while cap > 1 and sum(min(numel(v), cap) * itemsize(v) for _, v in arrays) > DUMP_BYTES:
+        cap //= 2
+    os.makedirs(directory, exist_ok=True)
+    manifest = {"cap_elements": cap, "arrays": {}}
+    for name, v in arrays:
+        entry = {"shape": list(v.shape), "source_dtype": str(v.dtype)}
+        if torch.is_tensor(v):
+            flat = v.detach().reshape(-1)
+            if flat.numel() > cap:
+                g = torch.Generator().manual_seed(zlib.crc32(name.encode()))
+                idx = torch.randint(0, flat.numel(), (cap,), generator=g).sort().values
+                flat = flat[idx.to(flat.device)]
+                entry["sample"] = {"elements": cap, "indices": "sorted torch.randint(0, numel, (elements,)) of torch.Generator().manual_seed(crc32(name)), flat order"}
+            else:
+                flat = flat.reshape(tuple(v.shape))
+            a = flat.to(torch.float32 if itemsize(v) == 4 else torch.float64).cpu().numpy()
+        else:
+            a = v
+        entry["dtype"] = str(a.dtype)
+        np.save(os.path.join(directory, f"{name}.npy"), a)
+        manifest["arrays"][name] = entry
+    with open(os.path.join(directory, "manifest.json"), "w") as fh:
+        json.dump(manifest, fh, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=10)
+    ap.add_argument("--steps", type=int, default=10, help="timed steps (>= 1)")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--batch", type=int, default=1, help="image pairs per step per GPU (configs[1] = 1)")
     ap.add_argument("--size", type=int, default=512)
     ap.add_argument("--precision", default="bf16x3", choices=["bf16", "bf16x3"], help="the timed mode (default: the 1e-3 parity mode)")
     ap.add_argument("--depth", type=int, default=1, help="steps in flight: 1 = one synchronous forward() per step (default); 2 = SIU3RModel.forward_async, "
                     "step n+1 is enqueued before step n's segment table is picked up on the host (measured: no gain, profiles/r04_pipeline_probe.txt)")
-    ap.add_argument("--no-second-mode", action="store_true")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-render", action="store_true")
+    ap.add_argument("--full", action="store_true", help="also the second precision mode, the roofline, the render legs and the CPU baselines")
+    ap.add_argument("--no-second-mode", action="store_true", help="(with --full)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(with --full)")
+    ap.add_argument("--no-roofline", action="store_true", help="(with --full)")
+    ap.add_argument("--no-render", action="store_true", help="(with --full)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the last timed step's outputs to DIR/<name>.npy (rank 0)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
 
     if not torch.cuda.is_available():
         raise RuntimeError("bench.py needs an MI355X: the HIP path has no CPU fallback")
@@ -208,6 +276,8 @@ def main():
         return model, step, dt, out
 
     model, step, dt, out = run_mode(args.precision)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(out, args.dump_outputs)
 
     # the path's single collective: per-rank additive statistics
     gauss = out[0]
@@ -216,7 +286,7 @@ def main():
     total = D.reduce_stats(D.all_gather_stats(D.pack_stats(stats), device=dev))
 
     second, m2, step2 = None, None, None
-    if not args.no_second_mode:
+    if args.full and not args.no_second_mode:
         other = "bf16" if args.precision == "bf16x3" else "bf16x3"
         m2, step2, dt2, out2 = run_mode(other)
         second = {"precision": other, "value": B * args.steps * world / dt2, "unit": "image-pairs/s", "ms_per_step": dt2 / args.steps * 1e3,
@@ -249,15 +319,15 @@ def main():
     if second:
         result["second_mode"] = second
 
-    if not args.no_roofline:
+    if args.full and not args.no_roofline:
         result["roofline"] = gemm_roofline(model, step, args.precision, B, H, W)
         if second and m2 is not None:
             second["roofline"] = gemm_roofline(m2, step2, second["precision"], B, H, W)
 
-    if not args.no_render:
+    if args.full and not args.no_render:
         result.update(render_legs(gauss, B, H, W, dev, world, step=step))
 
-    if world == 1 and not args.no_cpu_baseline:
+    if args.full and world == 1 and not args.no_cpu_baseline:
         result["cpu_baseline"] = cpu_baselines(images, K, H, W)
     print(json.dumps(result))
 

@@ -5,7 +5,7 @@ the image lacks (jaxtyping, lightning_utilities, hydra, omegaconf, dacite) so th
 ``/root/reference/src/models`` imports unmodified, exactly as SURVEY.md section 8(c)
 describes.  Nothing here is imported by the product path, by ``-m gpu`` tests, by
 ``bench.py`` or by ``smoke()`` -- /root/reference does not exist on the GPU box.
-Only ``tests/golden/make_golden.py`` and the container-only pin tests use it.
+Only the fixture generators under ``tests/golden/`` use it.
 """
 import os
 import sys

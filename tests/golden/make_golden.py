@@ -25,6 +25,7 @@ sys.path.insert(0, HERE)
 
 import _ref_import as R  # noqa: E402
 from crafted import crafted_panoptic_inputs, permuted  # noqa: E402
+from golden_utils import save_npz  # noqa: E402  (fixtures above 1 MiB are split into part files)
 from oracle import weights as OW  # noqa: E402
 
 STRIDE = 4093  # prime stride for the sampled tensors
@@ -89,7 +90,7 @@ def model_fixture(size, sd):
     out["qcl.sample"] = qcl.reshape(-1)[::STRIDE].numpy()
     out["qcl.l2"] = np.asarray(float(qcl.double().norm()))
     out["image.small"] = torch.nn.functional.interpolate(img[0], size=(32, 32), mode="area").numpy()  # input checksum aid
-    np.savez_compressed(os.path.join(HERE, f"model_{size}.npz"), **out)
+    save_npz(f"model_{size}", out, HERE)
     with open(os.path.join(HERE, f"model_{size}.json"), "w") as fh:
         json.dump(dict(seg_infos=infos, query_scores=qs, input="assets/living_room_image{1,2}.jpg, /255, bilinear to size",
                        intrinsics="fx=fy=318/256, c=0.5", weights="oracle.weights.make_weights(0)", stride=STRIDE), fh)
@@ -128,11 +129,33 @@ def multi_fixture(sd, size=128, V=3):
     out["qcl.shape"] = np.asarray(qcl.shape)
     out["qcl.sample"] = qcl.reshape(-1)[::STRIDE].numpy()
     out["qcl.l2"] = np.asarray(float(qcl.double().norm()))
-    np.savez_compressed(os.path.join(HERE, f"model_multi_v{V}_{size}.npz"), **out)
+    save_npz(f"model_multi_v{V}_{size}", out, HERE)
     with open(os.path.join(HERE, f"model_multi_v{V}_{size}.json"), "w") as fh:
         json.dump(dict(seg_infos=infos, query_scores=qs, input="golden_utils.multi_views of the asset pair, /255, bilinear to size", views=V,
                        intrinsics="fx=fy=318/256, c=0.5", weights="oracle.weights.make_weights(0)", stride=STRIDE), fh)
     print("multi-view fixture done", V, size, [len(i) for i in infos])
+
+
+def pin_fixture(sd, size=128):
+    """tests/test_oracle_pins.py: the reference model's state_dict spec (names, shapes, dtypes) and its forward on a seeded uniform pair
+    (torch.rand, seed 0) with make_weights(0).  Gaussian fields and both logit tensors whole, the harmonics as strided samples + a dense
+    window + norms (all of them: 9.8 MB)."""
+    model = R.build_reference_model((size, size))
+    spec = [[k, list(v.shape), str(v.dtype)] for k, v in model.state_dict().items()]
+    model.load_state_dict(sd, strict=True)
+    img = torch.rand(1, 2, 3, size, size, generator=torch.Generator().manual_seed(0))
+    K = torch.tensor([[318 / 256, 0, 0.5], [0, 318 / 256, 0.5], [0, 0, 1]])[None, None].repeat(1, 2, 1, 1)
+    with torch.no_grad():
+        g, seg, masks, infos, qs = model(img, K, enable_query_class_logit_lift=True)
+    out = {f: getattr(g, f).numpy() for f in ("means", "covariances", "opacities", "scales", "rotations")}
+    out.update((f"harmonics.{k}", np.asarray(v)) for k, v in summarize(g.harmonics).items())
+    out["class_queries_logits"] = seg.class_queries_logits.numpy()
+    out["masks_queries_logits"] = seg.masks_queries_logits.numpy()
+    save_npz(f"pin_{size}", out, HERE)
+    with open(os.path.join(HERE, f"pin_{size}.json"), "w") as fh:
+        json.dump(dict(state_dict=spec, seg_infos=infos, input="torch.rand(1, 2, 3, size, size), torch.Generator seed 0",
+                       intrinsics="fx=fy=318/256, c=0.5", weights="oracle.weights.make_weights(0)", stride=STRIDE), fh)
+    print("pin fixture done", size, [len(i) for i in infos])
 
 
 def panoptic_fixture():
@@ -218,6 +241,9 @@ if __name__ == "__main__":
         panoptic_fixture()
         lifting_fixture()
     sd = OW.make_weights(0)
+    pin_fixture(sd)
+    if "pin" in sys.argv[1:]:          # `make_golden.py models pin`: only the fixture of tests/test_oracle_pins.py
+        sys.exit(0)
     multi_fixture(sd)
     multi_fixture(sd, size=256, V=8)   # BASELINE configs[4]'s network half (8 views), at 256^2: 20 s of reference CPU time
     if "multi" in sys.argv[1:]:        # `make_golden.py models multi`: only the multi-view fixtures

@@ -1,6 +1,7 @@
 """Helpers shared by the golden-fixture tests (oracle on CPU, HIP path on the GPU box)."""
 import json
 import os
+import re
 
 import numpy as np
 import torch
@@ -17,8 +18,57 @@ def window_of(numel):
     return (numel // 3) // 64 * 64, WINDOW
 
 
+PART_BYTES = 1 << 20  # a stored fixture file stays below 1 MiB: larger fixtures are split into <stem>.npz, <stem>.part1.npz, ...
+
+
+class Fixture(dict):
+    """the arrays of one fixture, merged over its part files (np.load's NpzFile interface as the tests use it)"""
+
+    @property
+    def files(self):
+        return list(self)
+
+
+def load_npz(stem):
+    """tests/golden/<stem>.npz and its part files <stem>.part1.npz, <stem>.part2.npz, ... as one Fixture"""
+    z, i, path = Fixture(), 0, os.path.join(GOLDEN, f"{stem}.npz")
+    while os.path.exists(path):
+        with np.load(path, allow_pickle=False) as part:
+            z.update((k, part[k]) for k in part.files)
+        i += 1
+        path = os.path.join(GOLDEN, f"{stem}.part{i}.npz")
+    assert z, f"no fixture tests/golden/{stem}.npz"
+    return z
+
+
+def save_npz(stem, arrays, directory=GOLDEN):
+    """np.savez_compressed of a fixture, split over part files of at most PART_BYTES each (arrays kept whole, in order)"""
+    import io
+
+    def packed(d):
+        b = io.BytesIO()
+        np.savez_compressed(b, **d)
+        return b.getvalue()
+
+    parts, cur = [], {}
+    for k, v in arrays.items():
+        if cur and len(packed({**cur, k: v})) > PART_BYTES:
+            parts.append(cur)
+            cur = {}
+        cur[k] = v
+    parts.append(cur)
+    for f in os.listdir(directory):
+        if re.fullmatch(re.escape(stem) + r"\.part\d+\.npz", f):
+            os.remove(os.path.join(directory, f))
+    for i, d in enumerate(parts):
+        data = packed(d)
+        assert len(data) <= PART_BYTES, f"{stem}: array(s) {list(d)} alone exceed {PART_BYTES} bytes compressed"
+        with open(os.path.join(directory, f"{stem}.npz" if i == 0 else f"{stem}.part{i}.npz"), "wb") as fh:
+            fh.write(data)
+
+
 def load_model_fixture(size):
-    z = np.load(os.path.join(GOLDEN, f"model_{size}.npz"), allow_pickle=False)
+    z = load_npz(f"model_{size}")
     meta = json.load(open(os.path.join(GOLDEN, f"model_{size}.json")))
     return z, meta
 
@@ -49,7 +99,7 @@ def fixture_images_multi(size=128, V=3):
 
 
 def load_multi_fixture(V=3, size=128):
-    z = np.load(os.path.join(GOLDEN, f"model_multi_v{V}_{size}.npz"), allow_pickle=False)
+    z = load_npz(f"model_multi_v{V}_{size}")
     return z, json.load(open(os.path.join(GOLDEN, f"model_multi_v{V}_{size}.json")))
 
 

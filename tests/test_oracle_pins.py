@@ -1,38 +1,38 @@
-"""Container-only pins (skipped where /root/reference is absent): the weight spec against the reference's own
-state_dict, and the oracle against a live forward of the imported reference model."""
+"""Pins of the oracle to the reference model, on stored vectors (tests/golden/pin_128.*, written by tests/golden/make_golden.py from
+the reference's own code): the weight spec against the reference's state_dict, and the oracle against the reference's forward."""
+import json
 import os
-import sys
 
-import pytest
 import torch
 
-HERE = os.path.dirname(os.path.abspath(__file__))
-sys.path.insert(0, os.path.join(HERE, "golden"))
-import _ref_import as R  # noqa: E402
-
-pytestmark = [pytest.mark.refpin, pytest.mark.skipif(not R.reference_available(), reason="/root/reference not present")]
+from golden_utils import GOLDEN, compare_summary, load_npz
 
 
 def test_weight_spec_and_forward_match_reference():
     from oracle import siu3r_oracle as O
     from oracle import weights as OW
 
+    z = load_npz("pin_128")
+    meta = json.load(open(os.path.join(GOLDEN, "pin_128.json")))
     sd = OW.make_weights(0)
-    model = R.build_reference_model((128, 128))
-    ref_sd = model.state_dict()
-    assert set(ref_sd) == set(sd)
-    assert all(tuple(ref_sd[k].shape) == tuple(sd[k].shape) and ref_sd[k].dtype == sd[k].dtype for k in ref_sd)
-    model.load_state_dict(sd, strict=True)
+    ref_spec = {k: (tuple(shape), dtype) for k, shape, dtype in meta["state_dict"]}
+    assert set(ref_spec) == set(sd)
+    assert all(ref_spec[k] == (tuple(sd[k].shape), str(sd[k].dtype)) for k in ref_spec)
     g = torch.Generator().manual_seed(0)
     img = torch.rand(1, 2, 3, 128, 128, generator=g)
     K = torch.tensor([[318 / 256, 0, 0.5], [0, 318 / 256, 0.5], [0, 0, 1]])[None, None].repeat(1, 2, 1, 1)
     with torch.no_grad():
-        ref = model(img, K, enable_query_class_logit_lift=True)
         out = O.model_forward(sd, img, K, keep_intermediates=False)
-    for f in ("means", "covariances", "harmonics", "opacities", "scales", "rotations"):
-        a, b = out[f], getattr(ref[0], f)
+    for f in ("means", "covariances", "opacities", "scales", "rotations"):
+        a, b = out[f], torch.from_numpy(z[f])
+        assert a.shape == b.shape, (f, a.shape, b.shape)
         assert float((a - b).abs().max()) <= 5e-5 * float(b.abs().max()), f
-    assert torch.equal(out["class_queries_logits"], ref[1].class_queries_logits)
-    assert torch.equal(out["masks_queries_logits"], ref[1].masks_queries_logits)
+    compare_summary("harmonics", out["harmonics"], z, 5e-5)  # (9.8 MB whole: strided samples + a dense window + the norm)
+    # the logits are bit-identical to the reference's at the thread count the vectors were recorded with; fp32 CPU sums reorder with
+    # the thread partition (1 / 3 threads: <= 2e-6 max-normalised), so the stored form bounds them at 1e-5
+    for f in ("class_queries_logits", "masks_queries_logits"):
+        a, b = out[f], torch.from_numpy(z[f])
+        assert a.shape == b.shape, (f, a.shape, b.shape)
+        assert float((a - b).abs().max()) <= 1e-5 * float(b.abs().max()), f
     strip = lambda segs: [[(s_["id"], s_["label_id"], s_["was_fused"]) for s_ in i] for i in segs]
-    assert strip(out["seg_infos"]) == strip(ref[3]) and len(ref[3][0]) >= 3
+    assert strip(out["seg_infos"]) == strip(meta["seg_infos"]) and len(meta["seg_infos"][0]) >= 3
