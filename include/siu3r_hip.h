@@ -377,6 +377,25 @@ int siu3r_raster_composite_feat_ws(const siu3r_raster_cam* cams_host, int V, con
 /* tuning / A-B switches of the rasterizer (not for concurrent use).  key 0: 1 = the 32-channel kernel for every N-channel composite, 0 =
  * default (matrix-core form where it applies); key 1: accumulator blocks per chunk of the matrix-core form (1 .. 6, default 6) */
 int siu3r_raster_tune(int key, int value);
+/* ---- K2 backward (mode 0 cameras only; additions of ABI 10, backward compatible).  The forward's state of the same call is reused:
+ * cams_dev, bin_start, entries, cap_e, rec, rect and the outputs image [V,3,H,W] (with background), depth [V,H,W], alpha [V,H,W].
+ * composite: upstream gradients g_image / g_depth / g_alpha (shapes of the outputs) -> grad [V, G, 10] fp32 (zeroed here) =
+ * d loss / d {mean2d x, y, conic a, b, c, opacity, r, g, b, depth} of every (view, Gaussian) record; float atomics, one per
+ * (tile, Gaussian, non-zero term) */
+int siu3r_raster_composite_rgb_bwd(const siu3r_raster_cam* cams_host, int V, const void* cams_dev, int64_t G, const int32_t* bin_start,
+                                   const void* entries, int64_t cap_e, const float* rec, const float* image, const float* depth, const float* alpha,
+                                   const float* g_image, const float* g_depth, const float* g_alpha, float* grad, void* stream);
+/* projection: grad [V, G, 10] -> g_means [G,3], g_cov [G, cov_stride] (stride 9: entries 0, 1, 2, 4, 5, 8, zeros elsewhere), g_opacities
+ * [G], g_colors (the layout and size of colors; sh_degree < 0: the precomputed [G,1,3] colours), summed over the views (no atomics);
+ * g_mean2d [V, G, 2] optional (pixel-space mean gradient); pose_part optional: [siu3r_raster_pose_partial_rows(G), V, 6] per-workgroup
+ * sums of d loss / d (rho, theta) of the left perturbation w2c <- exp(xi^) w2c (P moving with it), reduced by siu3r_raster_pose_reduce */
+int siu3r_raster_project_bwd(const siu3r_raster_cam* cams_host, int V, const void* cams_dev, int64_t G, const float* means, const float* cov,
+                             int cov_stride, const float* opacities, const float* colors, int channels, int sh_planar, const int32_t* rect,
+                             const float* grad, float* g_means, float* g_cov, float* g_opacities, float* g_colors, float* g_mean2d,
+                             float* pose_part, void* stream);
+int64_t siu3r_raster_pose_partial_rows(int64_t G);
+/* pose_part [nrows, V, 6] -> g_pose [V, 6] = (rho, theta) per view */
+int siu3r_raster_pose_reduce(int V, int64_t nrows, const float* pose_part, float* g_pose, void* stream);
 /* x *= s in place (the reference rescales the scene x10 in place, src/models/gaussian_renderer.py:43-46) */
 int siu3r_scale_inplace(float* x, int64_t n, float s, void* stream);
 /* query-class-logit lifting (reference src/pipeline.py:137-193): rendered [V,H,W,q*C] -> sem_id, ins_id int64 [V,H,W];

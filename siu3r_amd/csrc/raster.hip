@@ -34,10 +34,10 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "raster_shared.h"
 
 namespace {
 
-constexpr int TILE = 16;
 typedef siu3r_raster_cam Cam;
 
 // exp(x) for x <= 0 from correctly rounded fp32 operations only (fmaf == v_fma_f32; the same sequence in oracle/raster_ref.c, so
@@ -58,61 +58,12 @@ __device__ __forceinline__ float exp_det(float x) {
   p = __builtin_fmaf(p, f, 1.0f);
   return ldexpf(p, (int)n);
 }
-// the same value without a branch (the early return becomes a select; x > 0 or NaN: whatever exp_det returns, i.e. the same chain)
-__device__ __forceinline__ float exp_det_sel(float x) {
-  const float y = x * 1.4426950408889634f;
-  const float n = floorf(y + 0.5f);
-  const float f = y - n;
-  float p = 1.52527338e-5f;
-  p = __builtin_fmaf(p, f, 1.54035304e-4f);
-  p = __builtin_fmaf(p, f, 1.33335581e-3f);
-  p = __builtin_fmaf(p, f, 9.61812911e-3f);
-  p = __builtin_fmaf(p, f, 5.55041087e-2f);
-  p = __builtin_fmaf(p, f, 2.40226507e-1f);
-  p = __builtin_fmaf(p, f, 6.93147181e-1f);
-  p = __builtin_fmaf(p, f, 1.0f);
-  const float r = ldexpf(p, (int)n);
-  return x < -87.0f ? 0.0f : r;
-}
-// Mahalanobis half-form q = 0.5 (a dx^2 + c dy^2) + b dx dy of a pixel offset, in the shared fused order
-__device__ __forceinline__ float conic_sigma(float ca, float cb, float cc, float dx, float dy) {
-  const float q = __builtin_fmaf(cc * dy, dy, (ca * dx) * dx);
-  return __builtin_fmaf(cb * dx, dy, 0.5f * q);
-}
 
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
-// a c - b^2 of a conic without the cancellation of the naive form (Kahan's 2 x 2 determinant: the rounding error of b * b is recovered with
-// one fma; accurate to a few ulps of the RESULT).  The footprint tests that cut lists per quadrant divide by it: for a long thin splat
-// seen diagonally a c and b^2 agree to 1e-6 and the naive difference is off by tens of per cent -- a box computed too small would drop
-// entries that blend.
-__device__ __forceinline__ float conic_det(float a, float b, float c) {
-  const float w = b * b;
-  const float e = __builtin_fmaf(-b, b, w);
-  return __builtin_fmaf(a, c, -w) + e;
-}
 
-// ---- frame geometry shared by host and device ------------------------------------------------------------------
-constexpr int NB_MAX = 1024;            // coarse bins per view (LDS: 40 B per bin in bin_scatter_kernel)
+// ---- frame geometry shared by host and device (Geo, make_geo: raster_shared.h) ---------------------------------
 constexpr int RS_ITEMS = 16, RS_CH = 256 * RS_ITEMS;  // radix sort: keys per workgroup
 constexpr int BN_ITEMS = 8, BN_CH = 256 * BN_ITEMS;   // coarse binning: sorted Gaussians per workgroup
-struct Geo {
-  int gw, gh, T, cb, nbx, nby, NB;
-};
-__host__ __device__ inline Geo make_geo(int width, int height) {
-  Geo g;
-  g.gw = (width + TILE - 1) / TILE;
-  g.gh = (height + TILE - 1) / TILE;
-  g.T = g.gw * g.gh;
-  g.cb = 4;
-  for (;;) {
-    g.nbx = (g.gw + g.cb - 1) / g.cb;
-    g.nby = (g.gh + g.cb - 1) / g.cb;
-    g.NB = g.nbx * g.nby;
-    if (g.NB <= NB_MAX || g.cb >= 16) break;
-    g.cb *= 2;
-  }
-  return g;
-}
 
 __constant__ float c_SH_C2[5] = {1.0925484305920792f, -1.0925484305920792f, 0.31539156525252005f, -1.0925484305920792f, 0.5462742152960396f};
 __constant__ float c_SH_C3[7] = {-0.5900435899266435f, 2.890611442640554f, -0.4570457994644658f, 0.3731763325901154f, -0.4570457994644658f, 1.445305721320277f, -0.5900435899266435f};
@@ -683,11 +634,6 @@ __global__ __launch_bounds__(256) void bin_scatter_kernel(Geo geo, const uint32_
 #ifndef SIU3R_COMP_DBG
 #define SIU3R_COMP_DBG 0  // tuning builds (tools/ab_raster.sh): 1 = no blend walk (scan + stage only), 2 = no per-wave list building either
 #endif
-// does the packed bin-relative rect cover tile (rtx, rty) of the bin?
-__device__ __forceinline__ bool entry_covers(uint32_t pr, int rtx, int rty) {
-  const int x0 = pr & 31, y0 = (pr >> 5) & 31, x1 = (pr >> 10) & 31, y1 = (pr >> 15) & 31;
-  return rtx >= x0 && rtx < x1 && rty >= y0 && rty < y1;
-}
 
 // ---- K2 composite: colour [3,H,W] + depth + accumulated opacity (+ n_touched), fused with the per-tile filter -----
 constexpr int STG = 512;       // staging capacity (survivors awaiting the blend)

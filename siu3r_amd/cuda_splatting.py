@@ -52,9 +52,15 @@ def render_cuda(extrinsics, intrinsics, near, far, image_shape, background_color
     CUDA original's buffer resize is) / "deferred" / False: see raster._with_retry.  translation_scale: the extrinsics' translation is
     multiplied by it inside the pose preparation (SplattingCUDA.forward's x10 scene rescale, gaussian_renderer.py:43-44, without a copy).
     extrinsics / intrinsics on the GPU: consumed there (no read-back; near / far / background_color are small host-side parameters and
-    should be CPU tensors then -- GPU ones are fetched, which synchronises)."""
+    should be CPU tensors then -- GPU ones are fetched, which synchronises).
+    Gradients: with grad mode on, images and depths are differentiable w.r.t. the Gaussian means, covariances ([b,G,3,3]: the six
+    entries the forward reads), SH coefficients and opacities (HIP backward, csrc/raster_bwd.hip).  cam_rot_delta / cam_trans_delta
+    ([b,3] each, theta / rho): per-view gradient holders of a LEFT perturbation of the world->camera pose the render uses (translation
+    already scaled by translation_scale), w2c <- exp(xi^) w2c, xi = (trans, rot), taken at xi = 0; the render uses the extrinsics as given.
+    Views whose Gaussians are expanded from one tensor still render as one multi-view call; autograd sums their gradients."""
     assert use_sh or gaussian_sh_coefficients.shape[-1] == 1
-    assert cam_rot_delta is None and cam_trans_delta is None, "pose gradients are training-only (out of scope)"
+    if (cam_rot_delta is None) != (cam_trans_delta is None):
+        raise ValueError("pass cam_rot_delta and cam_trans_delta together (one se(3) update per view)")
     b = extrinsics.shape[0]
     h, w = image_shape
     n = gaussian_sh_coefficients.shape[-1]
@@ -100,9 +106,10 @@ def render_cuda(extrinsics, intrinsics, near, far, image_shape, background_color
         # repacking (:107,115) nor the 'g xyz n -> g n xyz' rearrangement (:65) is materialised
         sh_i = gaussian_sh_coefficients[i0]
         planar = sh_i.shape[-1] == 25
+        delta = None if cam_rot_delta is None else torch.cat((cam_trans_delta[i0:i1], cam_rot_delta[i0:i1]), dim=-1).float()
         out = raster.rasterize_views_k2(cams, gaussian_means[i0], gaussian_covariances[i0], sh_i if planar else sh_i.permute(0, 2, 1).contiguous(),
                                         gaussian_opacities[i0], want_n_touched=return_aux, entry_capacity=entry_capacity, sh_planar=planar,
-                                        check_overflow=check_overflow, pose_c2w=pose)
+                                        check_overflow=check_overflow, pose_c2w=pose, pose_delta=delta)
         images.append(out["image"])
         depths.append(out["depth"])
         aux.append(out)

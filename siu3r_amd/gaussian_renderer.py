@@ -40,7 +40,10 @@ class SplattingCUDA:
         IN PLACE on the Gaussians (:43-46).  Camera tensors on the GPU are consumed there: the x10 translation scale (:44), the inverse,
         the field of view and the projection matrix are derived inside the projection call (siu3r_raster_project_c2w) -- with
         deferred_overflow_check the whole forward enqueues without a host synchronisation
-        (tests/test_raster_gpu.py::test_splatting_forward_does_not_synchronise)."""
+        (tests/test_raster_gpu.py::test_splatting_forward_does_not_synchronise).
+        cam_rot_delta / cam_trans_delta [b,v,3]: per-view pose gradient holders, handed to render_cuda (left perturbation of the
+        world->camera pose that is rendered, i.e. of the x10-scaled scene: rho is in scaled units); the colour render is then
+        differentiable (synchronous overflow check: deferred_overflow_check with gradients raises)."""
         b, v, _, _ = extrinsics.shape
         on_dev = extrinsics.is_cuda and intrinsics.is_cuda
         if on_dev:
@@ -62,7 +65,8 @@ class SplattingCUDA:
                     self.background_color[None].repeat(v, 1), gaussians.means[i][None].expand(v, -1, -1),
                     gaussians.covariances[i][None].expand(v, -1, -1, -1), gaussians.harmonics[i][None].expand(v, -1, -1, -1),
                     gaussians.opacities[i][None].expand(v, -1), check_overflow="deferred" if self.deferred_overflow_check else True,
-                    translation_scale=t_scale)
+                    translation_scale=t_scale, cam_rot_delta=None if cam_rot_delta is None else cam_rot_delta[i],
+                    cam_trans_delta=None if cam_trans_delta is None else cam_trans_delta[i])
                 colors.append(c_i)
                 depths.append(d_i)
             color = torch.stack(colors).clamp_(0.0, 1.0)  # (:73) clamp is pure data conditioning on the output buffer

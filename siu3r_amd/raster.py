@@ -312,10 +312,89 @@ def _with_retry(run, entry_capacity, check_overflow):
 
 
 def rasterize_views_k2(cams: Sequence[RasterCam], means, cov6, shs, opacities, want_n_touched=True, entry_capacity=None,
-                       check_overflow=True, sh_planar=False, pose_c2w=None) -> Dict[str, torch.Tensor]:
+                       check_overflow=True, sh_planar=False, pose_c2w=None, pose_delta=None, means2d=None) -> Dict[str, torch.Tensor]:
     """V views of one Gaussian set.  means [G,3]; cov6 [G,6] (upper triangle) or [G,3,3]; shs [G,ncoef,3], or with sh_planar
     [G,3,25] (Gaussians.harmonics as stored); opacities [G] (fp32, GPU) -> image [V,3,H,W], radii [V,G,2] i32, depth [V,H,W],
-    opacity [V,H,W], n_touched [V,G] i32 (None when not wanted) + the call's state."""
+    opacity [V,H,W], n_touched [V,G] i32 (None when not wanted) + the call's state.
+
+    Differentiable when grad mode is on and means / cov6 / shs / opacities / pose_delta / means2d requires grad (_RasterizeK2; the
+    outputs are the same bits as without grad).  pose_delta [V,6] = (rho, theta): a left se(3) perturbation w2c <- exp(xi^) w2c of each
+    view, a gradient holder taken at xi = 0 (the render uses the poses as given).  means2d [G,k>=2]: a gradient holder that receives the
+    pixel-space mean gradient summed over the views (the caller scales it).  Every other call runs the plain forward."""
+    diff = (means, cov6, shs, opacities, pose_delta, means2d)
+    if torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in diff):
+        if check_overflow == "deferred":
+            raise ValueError('check_overflow="deferred" cannot be combined with gradients: the backward reuses the binning of the forward, which '
+                             "must be known complete (pass check_overflow=True)")
+        if pose_delta is not None and tuple(pose_delta.shape) != (len(cams), 6):
+            raise ValueError(f"pose_delta must be [V, 6] = (rho, theta) per view, got {tuple(pose_delta.shape)}")
+        kw = dict(want_n_touched=want_n_touched, entry_capacity=entry_capacity, sh_planar=sh_planar, pose_c2w=pose_c2w)
+        image, depth, opacity, radii, n_touched, st = _RasterizeK2.apply(list(cams), kw, means, cov6, shs, opacities, pose_delta, means2d)
+        return dict(image=image, radii=radii, depth=depth, opacity=opacity, n_touched=n_touched, state=st)
+    return _rasterize_views_k2(cams, means, cov6, shs, opacities, want_n_touched, entry_capacity, check_overflow, sh_planar, pose_c2w)
+
+
+class _RasterizeK2(torch.autograd.Function):
+    """The K2 forward (unchanged kernels, synchronous overflow check) and its HIP backward (csrc/raster_bwd.hip): composite backward ->
+    per-(view, Gaussian) screen-space gradients -> projection backward -> Gaussians, pose (rho, theta) per view, pixel-space means."""
+
+    @staticmethod
+    def forward(ctx, cams, kw, means, cov6, shs, opacities, pose_delta, means2d):
+        o = _rasterize_views_k2(cams, means.detach(), cov6.detach(), shs.detach(), opacities.detach(), check_overflow=True, **kw)
+        st = o["state"]
+        ctx.st, ctx.sh_planar = st, kw["sh_planar"]
+        ctx.shapes = [(t.shape, t.dtype) if isinstance(t, torch.Tensor) else None for t in (means, cov6, shs, opacities, pose_delta, means2d)]
+        # private copies of the totals the backward needs: callers may modify the returned maps in place (image.clamp_(0, 1))
+        ctx.save_for_backward(means, cov6, shs, opacities, o["image"].clone(), o["depth"].clone(), o["opacity"].clone())
+        nd = [o["radii"]] + ([o["n_touched"]] if o["n_touched"] is not None else [])
+        ctx.mark_non_differentiable(*nd)
+        return o["image"], o["depth"], o["opacity"], o["radii"], o["n_touched"], st
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_image, g_depth, g_opacity, _g_radii, _g_nt, _g_st):
+        means, cov6, shs, opacities, image, depth, opacity = ctx.saved_tensors
+        st = ctx.st
+        lib = _lib.lib()
+        V, G, dev = st["V"], st["G"], image.device
+        z = lambda ref, g: torch.zeros_like(ref) if g is None else g.detach().float().contiguous()
+        g_image, g_depth, g_opacity = z(image, g_image), z(depth, g_depth), z(opacity, g_opacity)
+        means_c, cov_c, shs_c, op_c = (t.detach().contiguous().float() for t in (means, cov6, shs, opacities))
+        ncoef = shs_c.shape[2] if ctx.sh_planar else shs_c.shape[1]
+        grad = torch.empty((V, G, 10), dtype=torch.float32, device=dev)
+        check(lib.siu3r_raster_composite_rgb_bwd(st["cams"], V, _p(st["cams_dev"]), G, _p(st["bin_start"]), _p(st["entries"]), st["cap_e"], _p(st["rec"]),
+                                                 _p(image), _p(depth), _p(opacity), _p(g_image), _p(g_depth), _p(g_opacity), _p(grad), _stream()))
+        need_pose, need_m2d = ctx.needs_input_grad[6], ctx.needs_input_grad[7]
+        g_means, g_cov, g_op, g_sh = torch.empty_like(means_c), torch.empty_like(cov_c), torch.empty_like(op_c), torch.empty_like(shs_c)
+        g_m2d = torch.zeros((V, G, 2), dtype=torch.float32, device=dev) if need_m2d else None  # (culled Gaussians: not written)
+        rows = int(lib.siu3r_raster_pose_partial_rows(G))
+        part = torch.empty((max(rows, 1), V, 6), dtype=torch.float32, device=dev) if need_pose else None
+        check(lib.siu3r_raster_project_bwd(st["cams"], V, _p(st["cams_dev"]), G, _p(means_c), _p(cov_c), _cov_stride(cov_c), _p(op_c), _p(shs_c), ncoef,
+                                           int(bool(ctx.sh_planar)), _p(st["rect"]), _p(grad), _p(g_means), _p(g_cov), _p(g_op), _p(g_sh), _p(g_m2d),
+                                           _p(part), _stream()))
+        g_pose = None
+        if need_pose:
+            g_pose = torch.empty((V, 6), dtype=torch.float32, device=dev)
+            if rows == 0:
+                part.zero_()
+            check(lib.siu3r_raster_pose_reduce(V, rows, _p(part), _p(g_pose), _stream()))
+        g_mean2d = None
+        if need_m2d:
+            shape, dtype = ctx.shapes[5]
+            g_mean2d = torch.zeros(shape, dtype=dtype, device=dev)
+            g_mean2d[:, :2] = g_m2d.sum(0).to(dtype)
+        out = []
+        for i, g in enumerate((g_means, g_cov, g_sh, g_op, g_pose)):
+            if not ctx.needs_input_grad[2 + i]:
+                out.append(None)
+                continue
+            shape, dtype = ctx.shapes[i]
+            out.append(g.reshape(shape).to(dtype))
+        return (None, None, *out, g_mean2d)
+
+
+def _rasterize_views_k2(cams: Sequence[RasterCam], means, cov6, shs, opacities, want_n_touched=True, entry_capacity=None,
+                       check_overflow=True, sh_planar=False, pose_c2w=None) -> Dict[str, torch.Tensor]:
     _gpu(means, cov6, shs, opacities)
     means, cov6, shs, opacities = (t.contiguous().float() for t in (means, cov6, shs, opacities))
     V, G, dev = len(cams), means.shape[0], means.device
