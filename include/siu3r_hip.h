@@ -371,6 +371,10 @@ int siu3r_raster_composite_feat(const siu3r_raster_cam* cams_host, int V, const 
  * feature value (0 * inf = NaN) in any listed Gaussian -- or in Gaussian 0 -- poisons pixels the 32-channel kernel leaves untouched:
  * callers that may hold non-finite features select the 32-channel kernel (tests/test_raster_gpu.py pins both behaviours). */
 int64_t siu3r_raster_composite_feat_ws_bytes(int width, int height, int V, int64_t cap_d);
+/* 1 when siu3r_raster_composite_feat_ws takes the matrix-core form for these arguments (and so leaves the per-quadrant lists in ws, which a
+ * backward may reuse), 0 when it falls back to the 32-channel kernel; evaluated with the current siu3r_raster_tune state */
+int siu3r_raster_composite_feat_ws_lists(int width, int height, int V, int64_t G, const float* feats, int channels, const void* ws, int64_t ws_bytes,
+                                         int64_t cap_d);
 int siu3r_raster_composite_feat_ws(const siu3r_raster_cam* cams_host, int V, const void* cams_dev, int64_t G, const int32_t* tile_start,
                                    const int32_t* ids, int64_t cap_d, const float* rec, const float* feats, int channels, float* out,
                                    float* out_alpha, void* ws, int64_t ws_bytes, void* stream);
@@ -396,6 +400,30 @@ int siu3r_raster_project_bwd(const siu3r_raster_cam* cams_host, int V, const voi
 int64_t siu3r_raster_pose_partial_rows(int64_t G);
 /* pose_part [nrows, V, 6] -> g_pose [V, 6] = (rho, theta) per view */
 int siu3r_raster_pose_reduce(int V, int64_t nrows, const float* pose_part, float* g_pose, void* stream);
+/* ---- gsplat-family backward (mode 1 cameras only; additions of ABI 10, backward compatible).  The forward's state of the same call is
+ * reused (cams_dev, rec, rect, bin lists / tile lists).  Gradients are those of the function the forward computes, on the branch it took.
+ * three-channel fused path (siu3r_raster_composite_rgb with mode-1 cameras): colors [V,H,W,3] and alphas [V,H,W] as the forward wrote them
+ * (no background), their upstream gradients -> grad [V, G, 10] (zeroed here; terms as siu3r_raster_composite_rgb_bwd, depth unused) */
+int siu3r_raster_composite_rgb_bwd_k3(const siu3r_raster_cam* cams_host, int V, const void* cams_dev, int64_t G, const int32_t* bin_start,
+                                      const void* entries, int64_t cap_e, const float* rec, const float* colors, const float* alphas,
+                                      const float* g_colors, const float* g_alphas, float* grad, void* stream);
+/* the per-8 x 8-quadrant lists of the N-channel composite (what siu3r_raster_composite_feat_ws builds into its workspace for C >= 32), for
+ * a backward whose forward ran without them; ws as siu3r_raster_composite_feat_ws (ws_bytes >= siu3r_raster_composite_feat_ws_bytes) */
+int siu3r_raster_quad_lists(const siu3r_raster_cam* cams_host, int V, const void* cams_dev, int64_t G, const int32_t* tile_start, const int32_t* ids,
+                            int64_t cap_d, const float* rec, void* ws, int64_t ws_bytes, void* stream);
+/* N-channel composite (either forward form: the quadrant lists give the same per-pixel walk): out [V,H,W,C], out_alpha [V,H,W], upstream
+ * gradients g_out / g_alpha -> grad [V, G, 10] (terms 0..5) and g_feats [G, C] (both zeroed here; float atomics).  Features must be finite. */
+int siu3r_raster_composite_feat_bwd(const siu3r_raster_cam* cams_host, int V, const void* cams_dev, int64_t G, const int32_t* tile_start,
+                                    const void* ws, int64_t cap_d, const float* rec, const float* feats, int channels, const float* out,
+                                    const float* out_alpha, const float* g_out, const float* g_alpha, float* grad, float* g_feats, void* stream);
+/* projection: grad [V, G, 10] -> g_means [G,3], g_cov [G, cov_stride] (stride 9: entries 0, 1, 2, 4, 5, 8, zeros elsewhere), g_opacities
+ * [G], g_colors [G,3] optional (the three-channel path's record colours), summed over the views; pose_part optional:
+ * [siu3r_raster_pose_partial_rows(G), V, 12] per-workgroup sums of d loss / d [R | t] of each world->camera matrix */
+int siu3r_raster_project_bwd_k3(const siu3r_raster_cam* cams_host, int V, const void* cams_dev, int64_t G, const float* means, const float* cov,
+                                int cov_stride, const int32_t* rect, const float* grad, float* g_means, float* g_cov, float* g_opacities,
+                                float* g_colors, float* pose_part, void* stream);
+/* pose_part [nrows, V, 12] -> g_viewmats [V, 4, 4] (bottom row zero) */
+int siu3r_raster_viewmat_reduce(int V, int64_t nrows, const float* pose_part, float* g_viewmats, void* stream);
 /* x *= s in place (the reference rescales the scene x10 in place, src/models/gaussian_renderer.py:43-46) */
 int siu3r_scale_inplace(float* x, int64_t n, float s, void* stream);
 /* query-class-logit lifting (reference src/pipeline.py:137-193): rendered [V,H,W,q*C] -> sem_id, ins_id int64 [V,H,W];
@@ -439,6 +467,12 @@ int siu3r_blend_background(float* colors, const float* alpha, const float* bg_ho
  * bg_dev = `channels` floats (any channel count) */
 int siu3r_sh_eval_dp(const float* means, const float* campos3_dev, const float* sh, int ncoef, int degree, float* rgb, int64_t G, void* stream);
 int siu3r_blend_background_dp(float* colors, const float* alpha, const float* bg_dev, int channels, int64_t pixels, void* stream);
+/* backward passes of the two helpers: g_cov6 [G,6] -> g_quats [G,4] (through the normalisation), g_scales [G,3]; g_rgb [G,3] -> g_sh
+ * [G,ncoef,3] (zero where a colour was clamped at 0 and past the degree), g_means [G,3] (through the view direction), g_campos3 [3] (device,
+ * zeroed here) */
+int siu3r_quat_scale_to_cov6_bwd(const float* quats_wxyz, const float* scales, const float* g_cov6, float* g_quats, float* g_scales, int64_t G, void* stream);
+int siu3r_sh_eval_bwd(const float* means, const float* campos3_dev, const float* sh, int ncoef, int degree, const float* g_rgb, float* g_sh, float* g_means,
+                      float* g_campos3, int64_t G, void* stream);
 
 #ifdef __cplusplus
 }

@@ -137,6 +137,14 @@ SIGNATURES = {
     "siu3r_raster_project_bwd": [C.POINTER(RasterCam), _I, _P, _L, _P, _P, _I, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "siu3r_raster_pose_partial_rows": [_L],
     "siu3r_raster_pose_reduce": [_I, _L, _P, _P, _P],
+    "siu3r_raster_composite_rgb_bwd_k3": [C.POINTER(RasterCam), _I, _P, _L, _P, _P, _L, _P, _P, _P, _P, _P, _P, _P],
+    "siu3r_raster_composite_feat_ws_lists": [_I, _I, _I, _L, _P, _I, _P, _L, _L],
+    "siu3r_raster_quad_lists": [C.POINTER(RasterCam), _I, _P, _L, _P, _P, _L, _P, _P, _L, _P],
+    "siu3r_raster_composite_feat_bwd": [C.POINTER(RasterCam), _I, _P, _L, _P, _P, _L, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P],
+    "siu3r_raster_project_bwd_k3": [C.POINTER(RasterCam), _I, _P, _L, _P, _P, _I, _P, _P, _P, _P, _P, _P, _P, _P],
+    "siu3r_raster_viewmat_reduce": [_I, _L, _P, _P, _P],
+    "siu3r_quat_scale_to_cov6_bwd": [_P, _P, _P, _P, _P, _L, _P],
+    "siu3r_sh_eval_bwd": [_P, _P, _P, _I, _I, _P, _P, _P, _P, _L, _P],
     "siu3r_lift_ids": [_P, _I, _I, _I, _I, _I, _F, _I, C.c_uint32, _P, _P, _P, _P, _P],
     "siu3r_panoptic_stage1": [_P] * 20 + [_I] * 9 + [_F, _F, _F, C.c_uint32, _P],
     "siu3r_panoptic_qcl": [_P, _P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P],

@@ -20,7 +20,12 @@ One extension, `finite_features` (default True).  For C >= 32 feature channels t
 8 x 8 quadrant takes part in every entry of the quadrant's list (weight 0 where the entry does not reach it; list tails padded with
 Gaussian 0's row): bit-identical to gsplat's per-pixel walk for finite features, but an inf / NaN feature value turns into NaN in pixels
 the Gaussian does not touch (0 * inf).  Callers whose features may be non-finite pass `finite_features=False` and get the 32-channel
-kernel, whose pixels only see the rows that blend into them (tests/test_raster_gpu.py::test_k3_composite_with_a_non_finite_feature_row)."""
+kernel, whose pixels only see the rows that blend into them (tests/test_raster_gpu.py::test_k3_composite_with_a_non_finite_feature_row).
+
+Gradients (grad mode on and an input requiring grad): colours and alphas are differentiable w.r.t. `means`, `quats` + `scales` or `covars`,
+`opacities`, `colors` (features [G,C], or SH [G,K,3] with `sh_degree`: also through the view direction), `viewmats` (on the SH route also
+through the camera centre inverse(viewmats)[:3, 3]) and `backgrounds`, as gsplat's are; `Ks` gets none.  HIP backward passes
+(csrc/raster_bwd_k3.hip, raster_bwd.hip); the forward bits are the same with and without grad.  Gradients of non-finite features are undefined."""
 from __future__ import annotations
 
 import torch
@@ -57,7 +62,7 @@ def rasterization(means, quats, scales, opacities, colors, viewmats, Ks, width, 
             for _ in range(V)]  # frame size / planes / thresholds; the pose fields are overwritten on the device
     bg = None
     if backgrounds is not None:
-        bg = backgrounds.detach().to(device=dev, dtype=torch.float32)
+        bg = backgrounds.to(device=dev, dtype=torch.float32)
         bg = bg[None].expand(V, -1) if bg.dim() == 1 else bg  # viewer.py:333 passes one [3] colour for its single camera
     meta = {"width": width, "height": height, "tile_size": 16, "n_cameras": V}
     if sh_degree is None:
@@ -73,7 +78,7 @@ def rasterization(means, quats, scales, opacities, colors, viewmats, Ks, width, 
         # view-dependent colours: colors = SH coefficients [G, K, 3]; directions from the camera centre = inverse(viewmat)[:3, 3]
         if colors.dim() != 3 or colors.shape[2] != 3 or colors.shape[1] < (sh_degree + 1) ** 2:
             raise ValueError(f"sh_degree={sh_degree} needs colors [G, K >= {(sh_degree + 1) ** 2}, 3], got {tuple(colors.shape)}")
-        vm = viewmats.detach().to(device=dev, dtype=torch.float32)
+        vm = viewmats.to(device=dev, dtype=torch.float32)  # (differentiable: the camera centre carries a gradient back to viewmats)
         campos = torch.linalg.inv(vm)[:, :3, 3].contiguous()  # [V, 3] on the device
         outs, als, radii = [], [], []
         for v in range(V):
@@ -84,7 +89,9 @@ def rasterization(means, quats, scales, opacities, colors, viewmats, Ks, width, 
             radii.append(o["radii"][0])
         out, alphas = torch.stack(outs), torch.stack(als)
         meta["radii"] = torch.stack(radii)
-    if bg is not None:
+    if bg is not None and torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in (out, alphas, bg)):
+        out = torch.stack([raster.blend_background(out[v], alphas[v], bg[v]) for v in range(V)])  # out of place: the same kernel on a copy
+    elif bg is not None:
         for v in range(V):
             raster.blend_background_(out[v], alphas[v], bg[v])
     return out, alphas[..., None], meta

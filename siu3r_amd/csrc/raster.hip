@@ -35,6 +35,7 @@
 
 #include "common.h"
 #include "raster_shared.h"
+#include "raster_quad_lists.h"
 
 namespace {
 
@@ -1159,63 +1160,7 @@ typedef __attribute__((address_space(3))) void* lds_ptr_t;
 // (one padded half pair per quadrant instead of one per batch).  Same arithmetic: per pixel the fmaf chain over the list in order.
 //
 // quadrant lists: region of tile t = qids[4 * tile_start[t], 4 * tile_start[t + 1]); quadrant q uses the q-th quarter of it, qcnt[t][q] entries.
-__global__ __launch_bounds__(256) void ql_build_kernel(const Cam* __restrict__ cams, Geo geo, const int32_t* __restrict__ tile_start,
-                                                       const int32_t* __restrict__ ids, int64_t cap_d, const float* __restrict__ rec, int64_t G,
-                                                       int32_t* __restrict__ qids, int32_t* __restrict__ qcnt) {
-  __shared__ int s_w[4][4];  // [quadrant][wave] survivors of the current slice
-  const int v = blockIdx.y, tile = blockIdx.x, tx = tile % geo.gw, ty = tile / geo.gw;
-  const Cam& c = cams[v];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int32_t* ts = tile_start + (int64_t)v * (geo.T + 2);
-  const int32_t* idp = ids + (int64_t)v * cap_d;
-  const int beg = ts[tile], end = ts[tile + 1], len = end - beg;
-  int32_t* qo = qids + (int64_t)v * 4 * cap_d + 4 * (int64_t)beg;
-  const float alpha_min = c.alpha_min;
-  const float tx0 = (float)(tx * TILE), ty0 = (float)(ty * TILE);
-  int run[4] = {0, 0, 0, 0};
-  for (int b = beg; b < end; b += 256) {
-    const int i = b + threadIdx.x;
-    unsigned bits = 0;
-    int id = 0;
-    if (i < end) {
-      id = idp[i];
-      const float4* rp = (const float4*)(rec + 12 * ((int64_t)v * G + id));
-      const float4 r0 = rp[0], r1 = rp[1];
-      // alpha >= alpha_min  <=>  sigma <= L = ln(opacity / alpha_min); on that ellipse |dx| <= sqrt(2 L c / det), |dy| <= sqrt(2 L a / det).
-      // Conservative (margins far above the rounding of exp_det and of this bound): an entry dropped here can never pass the per-pixel
-      // test of the composite, an entry kept needlessly only costs time.
-      const float det = conic_det(r1.x, r1.y, r1.z);
-      const float L = logf(r1.w / alpha_min) * 1.001f + 0.001f;
-      bits = 0xfu;
-      if (L < 0.f) bits = 0;
-      else if (det > 0.f && L == L) {
-        const float ex = sqrtf(2.0f * L * r1.z / det) + 0.01f, ey = sqrtf(2.0f * L * r1.x / det) + 0.01f;
-        if (ex == ex && ey == ey) {
-          const bool xl = r0.x - ex <= tx0 + 7.5f && r0.x + ex >= tx0 + 0.5f, xr = r0.x - ex <= tx0 + 15.5f && r0.x + ex >= tx0 + 8.5f;
-          const bool yt = r0.y - ey <= ty0 + 7.5f && r0.y + ey >= ty0 + 0.5f, yb = r0.y - ey <= ty0 + 15.5f && r0.y + ey >= ty0 + 8.5f;
-          bits = (xl && yt ? 1u : 0u) | (xr && yt ? 2u : 0u) | (xl && yb ? 4u : 0u) | (xr && yb ? 8u : 0u);
-        }
-      }
-    }
-    unsigned long long m[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      m[q] = __ballot((bits >> q) & 1u);
-      if (lane == 0) s_w[q][wave] = __popcll(m[q]);
-    }
-    __syncthreads();
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      int off = run[q] + __popcll(m[q] & ((1ull << lane) - 1ull));
-      for (int w = 0; w < wave; ++w) off += s_w[q][w];
-      if ((bits >> q) & 1u) qo[(int64_t)q * len + off] = id;
-      run[q] += s_w[q][0] + s_w[q][1] + s_w[q][2] + s_w[q][3];
-    }
-    __syncthreads();
-  }
-  if (threadIdx.x < 4) qcnt[((int64_t)v * geo.T + tile) * 4 + threadIdx.x] = run[threadIdx.x];
-}
-
+// (ql_build_kernel: raster_quad_lists.h, where the N-channel backward builds the same lists)
 template <int NP>
 __global__ __launch_bounds__(256, 2) void composite_feat5_kernel(const Cam* __restrict__ cams, Geo geo, const int32_t* __restrict__ tile_start,
                                                                  const int32_t* __restrict__ qids, const int32_t* __restrict__ qcnt, int64_t cap_d,
@@ -1673,16 +1618,27 @@ extern "C" int64_t siu3r_raster_composite_feat_ws_bytes(int width, int height, i
   return (int64_t)V * (16 * cap_d + 16 * (int64_t)geo.T);
 }
 
+// does siu3r_raster_composite_feat_ws take the matrix-core form (which leaves the per-quadrant lists in ws) for these arguments?
+static bool feat_ws_matrix_form(int width, int height, int V, int64_t G, const float* feats, int channels, const void* ws, int64_t ws_bytes, int64_t cap_d) {
+  const Geo geo = make_geo(width, height);
+  // (the matrix-core form addresses records and features through buffer resources: 32-bit byte offsets; rows need only 4-byte alignment)
+  const bool fits32 = (int64_t)V * G * 48 < (1ll << 31) * 2 - 64 && (int64_t)G * channels * 4 < (1ll << 31) * 2 - 64 && (((uintptr_t)feats) & 3) == 0;
+  const int64_t need = (int64_t)V * (16 * cap_d + 16 * (int64_t)geo.T);
+  return !(g_feat_form == 1 || channels < 32 || !fits32 || !ws || ws_bytes < need || (((uintptr_t)ws) & 3));
+}
+
+extern "C" int siu3r_raster_composite_feat_ws_lists(int width, int height, int V, int64_t G, const float* feats, int channels, const void* ws,
+                                                    int64_t ws_bytes, int64_t cap_d) {
+  return feat_ws_matrix_form(width, height, V, G, feats, channels, ws, ws_bytes, cap_d) ? 1 : 0;
+}
+
 extern "C" int siu3r_raster_composite_feat_ws(const siu3r_raster_cam* cams_host, int V, const void* cams_dev, int64_t G, const int32_t* tile_start,
                                               const int32_t* ids, int64_t cap_d, const float* rec, const float* feats, int channels, float* out,
                                               float* out_alpha, void* ws, int64_t ws_bytes, void* stream) {
   if (int rc = check_views(cams_host, V, "raster_composite_feat_ws")) return rc;
   SIU3R_CHECK(cams_dev && tile_start && (ids || cap_d == 0 || G == 0) && ((rec && feats) || G == 0) && out && channels > 0, "raster_composite_feat_ws: bad arguments");
   const Geo geo = make_geo(cams_host[0].width, cams_host[0].height);
-  // (the matrix-core form addresses records and features through buffer resources: 32-bit byte offsets; rows need only 4-byte alignment)
-  const bool fits32 = (int64_t)V * G * 48 < (1ll << 31) * 2 - 64 && (int64_t)G * channels * 4 < (1ll << 31) * 2 - 64 && (((uintptr_t)feats) & 3) == 0;
-  const int64_t need = (int64_t)V * (16 * cap_d + 16 * (int64_t)geo.T);
-  if (g_feat_form == 1 || channels < 32 || !fits32 || !ws || ws_bytes < need || (((uintptr_t)ws) & 3))
+  if (!feat_ws_matrix_form(cams_host[0].width, cams_host[0].height, V, G, feats, channels, ws, ws_bytes, cap_d))
     return siu3r_raster_composite_feat(cams_host, V, cams_dev, G, tile_start, ids, cap_d, rec, feats, channels, out, out_alpha, stream);
   hipStream_t s = (hipStream_t)stream;
   int32_t* qids = (int32_t*)ws;

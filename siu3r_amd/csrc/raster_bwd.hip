@@ -17,22 +17,17 @@
 // passes no gradient to the clamped component; a colour clamped at 0 passes none to its SH coefficients.
 #include "common.h"
 #include "raster_shared.h"
+#include "raster_bwd_shared.h"
 
 namespace {
 
 typedef siu3r_raster_cam Cam;
 
-// per-(view, Gaussian) gradient record written by the composite backward
-enum { GR_MX = 0, GR_MY, GR_CA, GR_CB, GR_CC, GR_OP, GR_R, GR_G, GR_B, GR_Z, GR_N };
-
-__device__ __forceinline__ float wave_sum(float x) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
-  return x;
-}
-
 // ---- composite backward ------------------------------------------------------------------------------------------------------------
 constexpr int BSTG = 256;  // entries staged per slice
+// K3 (compile time): the gsplat family's conventions on the same walk, as composite_rgb_kernel<NT, K3> -- pixel centres at +0.5, saturation
+// test nT <= t_min, channel-last [V,H,W,3] colours and their gradient, no depth (depth / g_depth unused), no background (blended outside).
+template <bool K3 = false>
 __global__ __launch_bounds__(256) void composite_rgb_bwd_kernel(const Cam* __restrict__ cams, Geo geo, const int32_t* __restrict__ bin_start,
                                                                 const uint2* __restrict__ entries, int64_t cap_e, const float* __restrict__ rec, int64_t G,
                                                                 const float* __restrict__ image, const float* __restrict__ depth,
@@ -54,7 +49,7 @@ __global__ __launch_bounds__(256) void composite_rgb_bwd_kernel(const Cam* __res
   const int lx = (lane & 7) + 8 * (wave & 1), ly = (lane >> 3) + 8 * (wave >> 1);
   const int px = tx * TILE + lx, py = ty * TILE + ly;
   const bool inside = px < c.width && py < c.height;
-  const float pxf = (float)px, pyf = (float)py;
+  const float pxf = (float)px + (K3 ? 0.5f : 0.0f), pyf = (float)py + (K3 ? 0.5f : 0.0f);
   const int64_t ebeg = bin_start[v * (geo.NB + 1) + bin];
   const int64_t eend = min((int64_t)bin_start[v * (geo.NB + 1) + bin + 1], cap_e);
   const uint2* ep = entries + (int64_t)v * cap_e;
@@ -64,7 +59,18 @@ __global__ __launch_bounds__(256) void composite_rgb_bwd_kernel(const Cam* __res
   const int wbit = 1 << wave;
   // upstream gradients and the forward's totals of this pixel
   float gC0 = 0.f, gC1 = 0.f, gC2 = 0.f, gD = 0.f, gO = 0.f, tC0 = 0.f, tC1 = 0.f, tC2 = 0.f, tD = 0.f, tO = 0.f;
-  if (inside) {
+  if (inside && K3) {
+    const size_t hw = (size_t)c.width * c.height, pix = (size_t)py * c.width + px;
+    const size_t o = ((size_t)v * hw + pix) * 3;
+    gC0 = g_image[o];
+    gC1 = g_image[o + 1];
+    gC2 = g_image[o + 2];
+    gO = g_alpha[(size_t)v * hw + pix];
+    tC0 = image[o];
+    tC1 = image[o + 1];
+    tC2 = image[o + 2];
+    tO = alpha[(size_t)v * hw + pix];
+  } else if (inside) {
     const size_t hw = (size_t)c.width * c.height, pix = (size_t)py * c.width + px;
     gC0 = g_image[(size_t)v * 3 * hw + pix];
     gC1 = g_image[(size_t)v * 3 * hw + hw + pix];
@@ -112,7 +118,7 @@ __global__ __launch_bounds__(256) void composite_rgb_bwd_kernel(const Cam* __res
       if (L <= 0.f) {
         mk = 0;
       } else if (det > 0.f) {
-        const float ex = sqrtf(2.f * L * r1.z / det) * 1.01f + 0.05f, ey = sqrtf(2.f * L * r1.x / det) * 1.01f + 0.05f;
+        const float ex = sqrtf(2.f * L * r1.z / det) * 1.01f + (K3 ? 0.55f : 0.05f), ey = sqrtf(2.f * L * r1.x / det) * 1.01f + (K3 ? 0.55f : 0.05f);
         const float x0 = r0.x - ex - tile_x0, x1 = r0.x + ex - tile_x0, y0 = r0.y - ey - tile_y0, y1 = r0.y + ey - tile_y0;
         const int cx = (x0 <= 7.f && x1 >= 0.f ? 1 : 0) | (x0 <= 15.f && x1 >= 8.f ? 2 : 0);
         const int cy = (y0 <= 7.f && y1 >= 0.f ? 1 : 0) | (y0 <= 15.f && y1 >= 8.f ? 2 : 0);
@@ -134,7 +140,7 @@ __global__ __launch_bounds__(256) void composite_rgb_bwd_kernel(const Cam* __res
         const float a = fminf(alpha_max, Q.w * ex);
         const float nT = __builtin_fmaf(-T, a, T);
         const bool reach = !done && !(power > 0.0f) && !(a < alpha_min);
-        const bool sat = reach && nT < t_min;
+        const bool sat = reach && (K3 ? (nT <= t_min) : (nT < t_min));
         done = done || sat;
         const bool blend = reach && !sat;
         float gv[GR_N];
@@ -186,66 +192,6 @@ __global__ __launch_bounds__(256) void composite_rgb_bwd_kernel(const Cam* __res
       if (s != 0.f) atomicAdd(&grad[(vg + __float_as_int(s_a[j][3])) * GR_N + k], s);
     }
   }
-}
-
-// ---- SH basis with its gradient w.r.t. the (unit) view direction ---------------------------------------------------------------------
-struct Dual {  // value + d/dx, d/dy, d/dz
-  float v, x, y, z;
-};
-__device__ __forceinline__ Dual dconst(float c) { return {c, 0.f, 0.f, 0.f}; }
-__device__ __forceinline__ Dual operator+(Dual a, Dual b) { return {a.v + b.v, a.x + b.x, a.y + b.y, a.z + b.z}; }
-__device__ __forceinline__ Dual operator-(Dual a, Dual b) { return {a.v - b.v, a.x - b.x, a.y - b.y, a.z - b.z}; }
-__device__ __forceinline__ Dual operator-(Dual a, float b) { return {a.v - b, a.x, a.y, a.z}; }
-__device__ __forceinline__ Dual operator+(Dual a, float b) { return {a.v + b, a.x, a.y, a.z}; }
-__device__ __forceinline__ Dual operator*(float s, Dual a) { return {s * a.v, s * a.x, s * a.y, s * a.z}; }
-__device__ __forceinline__ Dual operator*(Dual a, Dual b) { return {a.v * b.v, a.x * b.v + a.v * b.x, a.y * b.v + a.v * b.y, a.z * b.v + a.v * b.z}; }
-
-__constant__ float c_B2[5] = {1.0925484305920792f, -1.0925484305920792f, 0.31539156525252005f, -1.0925484305920792f, 0.5462742152960396f};
-__constant__ float c_B3[7] = {-0.5900435899266435f, 2.890611442640554f, -0.4570457994644658f, 0.3731763325901154f, -0.4570457994644658f, 1.445305721320277f, -0.5900435899266435f};
-__constant__ float c_B4[9] = {2.5033429417967046f, -1.7701307697799304f, 0.9461746957575601f, -0.6690465435572892f, 0.10578554691520431f, -0.6690465435572892f, 0.47308734787878004f, -1.7701307697799304f, 0.6258357354491761f};
-
-// calls f(k, basis_k) for the coefficients the forward's polynomial uses (project_kernel: degree deg, band 4 only with band4); k is a
-// compile-time constant at every call site
-template <class F>
-__device__ __forceinline__ void sh_basis(float dx_, float dy_, float dz_, int deg, bool band4, F&& f) {
-  const Dual x = {dx_, 1.f, 0.f, 0.f}, y = {dy_, 0.f, 1.f, 0.f}, z = {dz_, 0.f, 0.f, 1.f};
-  f(0, dconst(0.28209479177387814f));
-  if (deg < 1) return;
-  const float C1 = 0.4886025119029199f;
-  f(1, -C1 * y);
-  f(2, C1 * z);
-  f(3, -C1 * x);
-  if (deg < 2) return;
-  const Dual xx = x * x, yy = y * y, zz = z * z, xy = x * y, yz = y * z, xz = x * z;
-  f(4, c_B2[0] * xy);
-  f(5, c_B2[1] * yz);
-  f(6, c_B2[2] * (2.0f * zz - xx - yy));
-  f(7, c_B2[3] * xz);
-  f(8, c_B2[4] * (xx - yy));
-  if (deg < 3) return;
-  f(9, c_B3[0] * (y * (3.0f * xx - yy)));
-  f(10, c_B3[1] * (xy * z));
-  f(11, c_B3[2] * (y * (4.0f * zz - xx - yy)));
-  f(12, c_B3[3] * (z * (2.0f * zz - 3.0f * xx - 3.0f * yy)));
-  f(13, c_B3[4] * (x * (4.0f * zz - xx - yy)));
-  f(14, c_B3[5] * (z * (xx - yy)));
-  f(15, c_B3[6] * (x * (xx - 3.0f * yy)));
-  if (deg < 4 || !band4) return;
-  f(16, c_B4[0] * (xy * (xx - yy)));
-  f(17, c_B4[1] * (yz * (3.0f * xx - yy)));
-  f(18, c_B4[2] * (xy * (7.0f * zz - 1.0f)));
-  f(19, c_B4[3] * (yz * (7.0f * zz - 3.0f)));
-  f(20, c_B4[4] * (zz * (35.0f * zz - 30.0f) + 3.0f));
-  f(21, c_B4[5] * (xz * (7.0f * zz - 3.0f)));
-  f(22, c_B4[6] * ((xx - yy) * (7.0f * zz - 1.0f)));
-  f(23, c_B4[7] * (xz * (xx - 3.0f * yy)));
-  f(24, c_B4[8] * (xx * (xx - 3.0f * yy) - yy * (3.0f * xx - yy)));
-}
-
-__device__ __forceinline__ void cross3(const float* a, const float* b, float* o) {
-  o[0] = a[1] * b[2] - a[2] * b[1];
-  o[1] = a[2] * b[0] - a[0] * b[2];
-  o[2] = a[0] * b[1] - a[1] * b[0];
 }
 
 // ---- projection backward -----------------------------------------------------------------------------------------------------------
@@ -506,9 +452,32 @@ extern "C" int siu3r_raster_composite_rgb_bwd(const siu3r_raster_cam* cams_host,
     return 2;
   }
   const Geo geo = make_geo(cams_host[0].width, cams_host[0].height);
-  hipLaunchKernelGGL(composite_rgb_bwd_kernel, dim3(geo.T, V), dim3(256), 0, s, (const Cam*)cams_dev, geo, bin_start, (const uint2*)entries, cap_e, rec, G,
+  hipLaunchKernelGGL(composite_rgb_bwd_kernel<false>, dim3(geo.T, V), dim3(256), 0, s, (const Cam*)cams_dev, geo, bin_start, (const uint2*)entries, cap_e, rec, G,
                      image, depth, alpha, g_image, g_depth, g_alpha, grad);
   SIU3R_LAUNCH_CHECK("siu3r_raster_composite_rgb_bwd");
+  return 0;
+}
+
+extern "C" int siu3r_raster_composite_rgb_bwd_k3(const siu3r_raster_cam* cams_host, int V, const void* cams_dev, int64_t G, const int32_t* bin_start,
+                                                 const void* entries, int64_t cap_e, const float* rec, const float* colors, const float* alphas,
+                                                 const float* g_colors, const float* g_alphas, float* grad, void* stream) {
+  SIU3R_CHECK(cams_host && V >= 1 && V <= 65535, "raster_composite_rgb_bwd_k3: bad view array (V = %d)", V);
+  for (int v = 0; v < V; ++v)
+    SIU3R_CHECK(cams_host[v].mode == 1 && cams_host[v].width == cams_host[0].width && cams_host[v].height == cams_host[0].height && cams_host[v].width > 0 &&
+                    cams_host[v].height > 0,
+                "raster_composite_rgb_bwd_k3: the gsplat family (mode 1) with one frame size per call");
+  SIU3R_CHECK(cams_dev && bin_start && colors && alphas && g_colors && g_alphas && (G == 0 || (entries && rec && grad)), "raster_composite_rgb_bwd_k3: null pointer");
+  SIU3R_CHECK(G >= 0 && G < (1ll << 31) && cap_e > 0, "raster_composite_rgb_bwd_k3: bad sizes");
+  hipStream_t s = (hipStream_t)stream;
+  if (G == 0) return 0;
+  if (hipMemsetAsync(grad, 0, sizeof(float) * GR_N * (size_t)V * G, s) != hipSuccess) {
+    siu3r_set_error("raster_composite_rgb_bwd_k3: memset failed");
+    return 2;
+  }
+  const Geo geo = make_geo(cams_host[0].width, cams_host[0].height);
+  hipLaunchKernelGGL(composite_rgb_bwd_kernel<true>, dim3(geo.T, V), dim3(256), 0, s, (const Cam*)cams_dev, geo, bin_start, (const uint2*)entries, cap_e, rec, G,
+                     colors, (const float*)nullptr, alphas, g_colors, (const float*)nullptr, g_alphas, grad);
+  SIU3R_LAUNCH_CHECK("siu3r_raster_composite_rgb_bwd_k3");
   return 0;
 }
 

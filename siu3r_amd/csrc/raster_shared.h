@@ -1,5 +1,5 @@
-// What the K2 composite (raster.hip) and its backward (raster_bwd.hip) must compute identically: the backward re-walks the forward's
-// per-pixel transmittance chain and has to stop at the same entry, so both translation units take these from one place.
+// What the composites (raster.hip) and their backward passes (raster_bwd.hip, raster_bwd_k3.hip) must compute identically: a backward
+// re-walks the forward's per-pixel transmittance chain and has to stop at the same entry, so the translation units take these from one place.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>

@@ -37,7 +37,8 @@ class SplattingCUDA:
                 cam_rot_delta=None, cam_trans_delta=None):
         """reference signature gaussian_renderer.py:29-41.  extrinsics [b,v,4,4] camera-to-world (OpenCV),
         intrinsics [b,v,3,3] normalised.  NOTE (quirk 1, reproduced): means / covariances are rescaled x10 / x100
-        IN PLACE on the Gaussians (:43-46).  Camera tensors on the GPU are consumed there: the x10 translation scale (:44), the inverse,
+        IN PLACE on the Gaussians (:43-46); when they require grad the rescale is recorded by autograd, as in the reference (render_qc_logits
+        is then differentiable w.r.t. means, covariances, opacities and seg_query_class_logits).  Camera tensors on the GPU are consumed there: the x10 translation scale (:44), the inverse,
         the field of view and the projection matrix are derived inside the projection call (siu3r_raster_project_c2w) -- with
         deferred_overflow_check the whole forward enqueues without a host synchronisation
         (tests/test_raster_gpu.py::test_splatting_forward_does_not_synchronise).
@@ -52,8 +53,14 @@ class SplattingCUDA:
             extrinsics = extrinsics.detach().float().cpu().clone()
             extrinsics[..., :3, 3] = extrinsics[..., :3, 3] * self.scale_factor
             intr, t_scale = intrinsics.detach().float().cpu(), 1.0
-        raster.scale_inplace_(gaussians.covariances, self.scale_factor ** 2)
-        raster.scale_inplace_(gaussians.means, self.scale_factor)
+        if torch.is_grad_enabled() and (gaussians.means.requires_grad or gaussians.covariances.requires_grad):
+            # (:45-46) the reference rescales with in-place torch products, which autograd records: the tensors upstream then receive x100 /
+            # x10 the gradient of the rescaled buffers.  Same product, same fp32 bits as the kernel; a leaf that requires grad raises there
+            gaussians.covariances.mul_(self.scale_factor ** 2)
+            gaussians.means.mul_(self.scale_factor)
+        else:
+            raster.scale_inplace_(gaussians.covariances, self.scale_factor ** 2)
+            raster.scale_inplace_(gaussians.means, self.scale_factor)
         near, far = 1.0, self.far * self.scale_factor
         color = depth = None
         all_qc: Optional[List[torch.Tensor]] = None

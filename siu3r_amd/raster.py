@@ -427,12 +427,112 @@ def tune(key: int, value: int) -> None:
     check(_lib.lib().siu3r_raster_tune(int(key), int(value)))
 
 
+def _wants_grad(*ts) -> bool:
+    return torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in ts)
+
+
+def _no_deferred(check_overflow):
+    if check_overflow == "deferred":
+        raise ValueError('check_overflow="deferred" cannot be combined with gradients: the backward reuses the binning of the forward, which '
+                         "must be known complete (pass check_overflow=True)")
+
+
 def rasterize_views_k3(cams: Sequence[RasterCam], means, cov6, opacities, feats, entry_capacity=None, pair_capacity=None,
                        check_overflow=True, pose_dev=None, matrix_form=True, pose_c2w=None) -> Dict[str, torch.Tensor]:
     """feats [G,C] -> colors [V,H,W,C], alphas [V,H,W] (+ state).  gsplat semantics: the per-tile lists are materialised once; for
     C >= 32 they are cut per 8 x 8 quadrant and blended on the matrix cores, all channels at once (identical bits for FINITE features).
     matrix_form=False: the 32-channel kernel, whose pixels only ever see the rows that blend into them -- for features that may hold
-    inf / NaN (include/siu3r_hip.h, siu3r_raster_composite_feat_ws)."""
+    inf / NaN (include/siu3r_hip.h, siu3r_raster_composite_feat_ws).
+
+    Differentiable when grad mode is on and means / cov6 / opacities / feats / the viewmats of pose_dev require grad (_RasterizeK3; the
+    outputs are the same bits as without grad).  The gradient is undefined for non-finite features.  Every other call runs the plain forward."""
+    vm = pose_dev[0] if pose_dev is not None else None
+    if _wants_grad(means, cov6, opacities, feats, vm):
+        _no_deferred(check_overflow)
+        kw = dict(entry_capacity=entry_capacity, pair_capacity=pair_capacity, matrix_form=matrix_form, pose_c2w=pose_c2w,
+                  Ks=None if pose_dev is None else pose_dev[1])
+        colors, alphas, radii, st = _RasterizeK3.apply(list(cams), kw, means, cov6, opacities, feats, vm)
+        return dict(colors=colors, alphas=alphas, radii=radii, state=st)
+    return _rasterize_views_k3(cams, means, cov6, opacities, feats, entry_capacity, pair_capacity, check_overflow, pose_dev, matrix_form, pose_c2w)
+
+
+def _grads_out(ctx, first, grads):
+    """the gradients of the differentiable inputs (index first.. of forward's arguments) in their shapes / dtypes / devices (a pose handed
+    over on the host gets its gradient there), None where not needed"""
+    out = []
+    for i, g in enumerate(grads):
+        if g is None or not ctx.needs_input_grad[first + i]:
+            out.append(None)
+            continue
+        shape, dtype, device = ctx.shapes[i]
+        out.append(g.reshape(shape).to(device=device, dtype=dtype))
+    return out
+
+
+def _project_bwd_k3(st, means, cov6, grad, need_pose, g_colors=None):
+    """the mode-1 projection backward of a finished composite backward (grad [V,G,10]) -> g_means, g_cov, g_opacities, g_viewmats [V,4,4]"""
+    lib = _lib.lib()
+    V, G, dev = st["V"], st["G"], means.device
+    g_means, g_cov, g_op = torch.empty_like(means), torch.empty_like(cov6), torch.empty((G,), dtype=torch.float32, device=dev)
+    rows = int(lib.siu3r_raster_pose_partial_rows(G))
+    part = torch.zeros((max(rows, 1), V, 12), dtype=torch.float32, device=dev) if need_pose else None
+    check(lib.siu3r_raster_project_bwd_k3(st["cams"], V, _p(st["cams_dev"]), G, _p(means), _p(cov6), _cov_stride(cov6), _p(st["rect"]), _p(grad),
+                                          _p(g_means), _p(g_cov), _p(g_op), _p(g_colors), _p(part), _stream()))
+    g_vm = None
+    if need_pose:
+        g_vm = torch.empty((V, 4, 4), dtype=torch.float32, device=dev)
+        check(lib.siu3r_raster_viewmat_reduce(V, rows, _p(part), _p(g_vm), _stream()))
+    return g_means, g_cov, g_op, g_vm
+
+
+class _RasterizeK3(torch.autograd.Function):
+    """The K3 N-channel forward (unchanged kernels, synchronous overflow check) and its HIP backward (csrc/raster_bwd_k3.hip): composite
+    backward over the per-quadrant lists (the forward's workspace, or built here) -> per-(view, Gaussian) screen-space gradients and the
+    feature gradient -> projection backward -> Gaussians and world->camera matrices."""
+
+    @staticmethod
+    def forward(ctx, cams, kw, means, cov6, opacities, feats, viewmats):
+        kw = dict(kw)
+        Ks = kw.pop("Ks")
+        pose_dev = None if viewmats is None else (viewmats, Ks)
+        o = _rasterize_views_k3(cams, means.detach(), cov6.detach(), opacities.detach(), feats.detach(), check_overflow=True, pose_dev=pose_dev, **kw)
+        ctx.st = o["state"]
+        ctx.shapes = [(t.shape, t.dtype, t.device) if isinstance(t, torch.Tensor) else None for t in (means, cov6, opacities, feats, viewmats)]
+        # private copies of the totals the backward needs: callers may modify the returned maps in place
+        ctx.save_for_backward(means, cov6, feats, o["colors"].clone(), o["alphas"].clone())
+        ctx.mark_non_differentiable(o["radii"])
+        return o["colors"], o["alphas"], o["radii"], o["state"]
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_colors, g_alphas, _g_radii, _g_st):
+        means, cov6, feats, colors, alphas = ctx.saved_tensors
+        st = ctx.st
+        lib = _lib.lib()
+        V, G, dev = st["V"], st["G"], colors.device
+        z = lambda ref, g: torch.zeros_like(ref) if g is None else g.detach().float().contiguous()
+        g_colors, g_alphas = z(colors, g_colors), z(alphas, g_alphas)
+        means_c, cov_c, feats_c = (t.detach().contiguous().float() for t in (means, cov6, feats))
+        Cc = feats_c.shape[1]
+        tstart, ids_all, cap_d = st["tile_start_all"], st["ids_all"], st["cap_d"]
+        # the per-quadrant lists: the forward's when its matrix-core form built them, else built now (whichever forward kernel ran -- the
+        # 32-channel one below 32 channels, after tune(0, 1) or for scenes past 32-bit offsets -- these lists give the same walk)
+        ws = st.get("feat_ws")
+        if not st.get("feat_ws_lists"):
+            if ws is None:
+                ws = torch.empty((int(lib.siu3r_raster_composite_feat_ws_bytes(st["W"], st["H"], V, cap_d)) // 4,), dtype=torch.int32, device=dev)
+            check(lib.siu3r_raster_quad_lists(st["cams"], V, _p(st["cams_dev"]), G, _p(tstart), _p(ids_all), cap_d, _p(st["rec"]), _p(ws),
+                                              ws.numel() * 4, _stream()))
+        grad = torch.empty((V, G, 10), dtype=torch.float32, device=dev)
+        g_feats = torch.empty_like(feats_c)
+        check(lib.siu3r_raster_composite_feat_bwd(st["cams"], V, _p(st["cams_dev"]), G, _p(tstart), _p(ws), cap_d, _p(st["rec"]), _p(feats_c), Cc,
+                                                  _p(colors), _p(alphas), _p(g_colors), _p(g_alphas), _p(grad), _p(g_feats), _stream()))
+        g_means, g_cov, g_op, g_vm = _project_bwd_k3(st, means_c, cov_c, grad, ctx.needs_input_grad[6])
+        return (None, None, *_grads_out(ctx, 2, (g_means, g_cov, g_op, g_feats, g_vm)))
+
+
+def _rasterize_views_k3(cams: Sequence[RasterCam], means, cov6, opacities, feats, entry_capacity=None, pair_capacity=None,
+                        check_overflow=True, pose_dev=None, matrix_form=True, pose_c2w=None) -> Dict[str, torch.Tensor]:
     _gpu(means, cov6, opacities, feats)
     if check_overflow == "deferred":
         raise ValueError('check_overflow="deferred" is only safe on the RGB composites (an overflowing view is NaN-poisoned there); the '
@@ -451,6 +551,8 @@ def rasterize_views_k3(cams: Sequence[RasterCam], means, cov6, opacities, feats,
         # workspace of the per-quadrant lists (C >= 32: every wave of the composite walks its own 8 x 8 quadrant's list)
         ws = torch.empty((int(lib.siu3r_raster_composite_feat_ws_bytes(W, H, V, cap_d)) // 4,), dtype=torch.int32, device=dev) if (Cc >= 32 and matrix_form) else None
         st["feat_ws"] = ws
+        # (whether the forward leaves the per-quadrant lists in ws: a backward reuses them instead of building them again)
+        st["feat_ws_lists"] = ws is not None and bool(lib.siu3r_raster_composite_feat_ws_lists(W, H, V, G, _p(feats), Cc, _p(ws), ws.numel() * 4, cap_d))
         check(lib.siu3r_raster_composite_feat_ws(st["cams"], V, _p(st["cams_dev"]), G, _p(tstart), _p(ids_all), cap_d, _p(st["rec"]), _p(feats), Cc,
                                                  _p(out), _p(alpha), _p(ws), 0 if ws is None else ws.numel() * 4, _stream()))
         return dict(colors=out, alphas=alpha, radii=st["radii"], state=st)
@@ -462,7 +564,54 @@ def rasterize_views_k3_rgb(cams: Sequence[RasterCam], means, cov6, opacities, rg
                            pose_dev=None) -> Dict[str, torch.Tensor]:
     """gsplat semantics with THREE precomputed colour channels (rgb [G,3]) -> colors [V,H,W,3], alphas [V,H,W] (+ state), through the
     fused sort-free composite: the colour travels in the per-Gaussian record and no per-tile list is written to HBM (the N-channel
-    path materialises the lists because every 32-channel chunk re-walks them)."""
+    path materialises the lists because every 32-channel chunk re-walks them).
+
+    Differentiable when grad mode is on and means / cov6 / opacities / rgb / the viewmats of pose_dev require grad (_RasterizeK3RGB)."""
+    vm = pose_dev[0] if pose_dev is not None else None
+    if _wants_grad(means, cov6, opacities, rgb, vm):
+        _no_deferred(check_overflow)
+        kw = dict(entry_capacity=entry_capacity, Ks=None if pose_dev is None else pose_dev[1])
+        colors, alphas, radii, st = _RasterizeK3RGB.apply(list(cams), kw, means, cov6, opacities, rgb, vm)
+        return dict(colors=colors, alphas=alphas, radii=radii, state=st)
+    return _rasterize_views_k3_rgb(cams, means, cov6, opacities, rgb, entry_capacity, check_overflow, pose_dev)
+
+
+class _RasterizeK3RGB(torch.autograd.Function):
+    """The K3 three-channel fused forward and its HIP backward: composite_rgb_bwd_kernel<K3> (csrc/raster_bwd.hip) re-walks the coarse
+    bins like the forward, then the mode-1 projection backward (csrc/raster_bwd_k3.hip) takes the record colours' gradient to rgb."""
+
+    @staticmethod
+    def forward(ctx, cams, kw, means, cov6, opacities, rgb, viewmats):
+        kw = dict(kw)
+        Ks = kw.pop("Ks")
+        pose_dev = None if viewmats is None else (viewmats, Ks)
+        o = _rasterize_views_k3_rgb(cams, means.detach(), cov6.detach(), opacities.detach(), rgb.detach(), check_overflow=True, pose_dev=pose_dev, **kw)
+        ctx.st = o["state"]
+        ctx.shapes = [(t.shape, t.dtype, t.device) if isinstance(t, torch.Tensor) else None for t in (means, cov6, opacities, rgb, viewmats)]
+        ctx.save_for_backward(means, cov6, o["colors"].clone(), o["alphas"].clone())
+        ctx.mark_non_differentiable(o["radii"])
+        return o["colors"], o["alphas"], o["radii"], o["state"]
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_colors, g_alphas, _g_radii, _g_st):
+        means, cov6, colors, alphas = ctx.saved_tensors
+        st = ctx.st
+        lib = _lib.lib()
+        V, G, dev = st["V"], st["G"], colors.device
+        z = lambda ref, g: torch.zeros_like(ref) if g is None else g.detach().float().contiguous()
+        g_colors, g_alphas = z(colors, g_colors), z(alphas, g_alphas)
+        means_c, cov_c = means.detach().contiguous().float(), cov6.detach().contiguous().float()
+        grad = torch.empty((V, G, 10), dtype=torch.float32, device=dev)
+        check(lib.siu3r_raster_composite_rgb_bwd_k3(st["cams"], V, _p(st["cams_dev"]), G, _p(st["bin_start"]), _p(st["entries"]), st["cap_e"],
+                                                    _p(st["rec"]), _p(colors), _p(alphas), _p(g_colors), _p(g_alphas), _p(grad), _stream()))
+        g_rgb = torch.empty((G, 3), dtype=torch.float32, device=dev)
+        g_means, g_cov, g_op, g_vm = _project_bwd_k3(st, means_c, cov_c, grad, ctx.needs_input_grad[6], g_colors=g_rgb)
+        return (None, None, *_grads_out(ctx, 2, (g_means, g_cov, g_op, g_rgb, g_vm)))
+
+
+def _rasterize_views_k3_rgb(cams: Sequence[RasterCam], means, cov6, opacities, rgb, entry_capacity=None, check_overflow=True,
+                            pose_dev=None) -> Dict[str, torch.Tensor]:
     _gpu(means, cov6, opacities, rgb)
     means, cov6, opacities, rgb = (t.contiguous().float() for t in (means, cov6, opacities, rgb))
     assert rgb.shape[1] == 3
@@ -493,7 +642,13 @@ def scale_inplace_(x: torch.Tensor, s: float):
 
 
 def quat_scale_to_cov6(quats_wxyz: torch.Tensor, scales: torch.Tensor) -> torch.Tensor:
-    """[G,4] (w,x,y,z) + [G,3] -> [G,6] (gsplat's quat_scale_to_covar, upper triangle)."""
+    """[G,4] (w,x,y,z) + [G,3] -> [G,6] (gsplat's quat_scale_to_covar, upper triangle).  Differentiable (through the normalisation)."""
+    if _wants_grad(quats_wxyz, scales):
+        return _QuatScaleCov6.apply(quats_wxyz, scales)
+    return _quat_scale_to_cov6(quats_wxyz, scales)
+
+
+def _quat_scale_to_cov6(quats_wxyz, scales):
     _gpu(quats_wxyz, scales)
     q, sc = quats_wxyz.contiguous().float(), scales.contiguous().float()
     out = torch.empty((q.shape[0], 6), dtype=torch.float32, device=q.device)
@@ -501,9 +656,36 @@ def quat_scale_to_cov6(quats_wxyz: torch.Tensor, scales: torch.Tensor) -> torch.
     return out
 
 
+class _QuatScaleCov6(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, quats, scales):
+        ctx.save_for_backward(quats, scales)
+        return _quat_scale_to_cov6(quats.detach(), scales.detach())
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_cov6):
+        quats, scales = ctx.saved_tensors
+        q, sc = quats.detach().contiguous().float(), scales.detach().contiguous().float()
+        gq, gs = torch.empty_like(q), torch.empty_like(sc)
+        check(_lib.lib().siu3r_quat_scale_to_cov6_bwd(_p(q), _p(sc), _p(g_cov6.detach().float().contiguous()), _p(gq), _p(gs), q.shape[0], _stream()))
+        return (gq.to(quats.dtype) if ctx.needs_input_grad[0] else None, gs.to(scales.dtype) if ctx.needs_input_grad[1] else None)
+
+
 def sh_eval(means: torch.Tensor, campos, sh: torch.Tensor, degree: int) -> torch.Tensor:
     """means [G,3], campos (3 floats on the host, or a DEVICE tensor of 3 floats: no read-back), sh [G,ncoef,3] -> rgb [G,3] =
-    max(SH . coeffs + 0.5, 0)."""
+    max(SH . coeffs + 0.5, 0).  Differentiable w.r.t. means, sh and a device campos (zero gradient where a colour was clamped at 0)."""
+    cp_t = campos if isinstance(campos, torch.Tensor) else None
+    if _wants_grad(means, sh, cp_t):
+        if cp_t is None:
+            cp_t = torch.tensor([float(v) for v in campos], dtype=torch.float32, device=means.device)
+        elif not cp_t.is_cuda:  # (a differentiable copy: a host campos that requires grad gets its gradient back on the host)
+            cp_t = cp_t.to(device=means.device, dtype=torch.float32)
+        return _ShEval.apply(means, cp_t, sh, int(degree))
+    return _sh_eval(means, campos, sh, degree)
+
+
+def _sh_eval(means, campos, sh, degree):
     _gpu(means, sh)
     means, sh = means.contiguous().float(), sh.contiguous().float()
     out = torch.empty((means.shape[0], 3), dtype=torch.float32, device=means.device)
@@ -515,6 +697,26 @@ def sh_eval(means: torch.Tensor, campos, sh: torch.Tensor, degree: int) -> torch
     cam = (C.c_float * 3)(*[float(v) for v in campos])
     check(_lib.lib().siu3r_sh_eval(_p(means), C.cast(cam, C.c_void_p), _p(sh), sh.shape[1], int(degree), _p(out), means.shape[0], _stream()))
     return out
+
+
+class _ShEval(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, means, campos, sh, degree):
+        ctx.save_for_backward(means, campos, sh)
+        ctx.degree = degree
+        return _sh_eval(means.detach(), campos.detach(), sh.detach(), degree)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_rgb):
+        means, campos, sh = ctx.saved_tensors
+        m, cp, s = (t.detach().contiguous().float() for t in (means, campos, sh))
+        g_m, g_sh, g_cp = torch.empty_like(m), torch.empty_like(s), torch.empty((3,), dtype=torch.float32, device=m.device)
+        check(_lib.lib().siu3r_sh_eval_bwd(_p(m), _p(cp), _p(s), s.shape[1], ctx.degree, _p(g_rgb.detach().float().contiguous()), _p(g_sh), _p(g_m),
+                                           _p(g_cp), m.shape[0], _stream()))
+        need = ctx.needs_input_grad
+        return (g_m.to(means.dtype) if need[0] else None, g_cp.reshape(campos.shape).to(campos.dtype) if need[1] else None,
+                g_sh.to(sh.dtype) if need[2] else None, None)
 
 
 def blend_background_(colors: torch.Tensor, alphas: torch.Tensor, bg) -> torch.Tensor:
@@ -529,6 +731,30 @@ def blend_background_(colors: torch.Tensor, alphas: torch.Tensor, bg) -> torch.T
     b = (C.c_float * 3)(*([float(v) for v in bg] + [0.0] * (3 - len(bg))))
     check(_lib.lib().siu3r_blend_background(_p(colors), _p(alphas), C.cast(b, C.c_void_p), colors.shape[-1], alphas.numel(), _stream()))
     return colors
+
+
+def blend_background(colors: torch.Tensor, alphas: torch.Tensor, bg: torch.Tensor) -> torch.Tensor:
+    """Out-of-place, differentiable form of blend_background_ (the same kernel on a copy: the same bits): colors [...,C] + (1 - alphas[...])
+    * bg [C] (a device tensor).  Gradients reach colors, alphas and bg."""
+    return _BlendBackground.apply(colors, alphas, bg)
+
+
+class _BlendBackground(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, colors, alphas, bg):
+        ctx.save_for_backward(alphas, bg)
+        out = colors.detach().float().contiguous().clone()
+        return blend_background_(out, alphas.detach().float().contiguous(), bg.detach())
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        # d out / d colors = 1, d out / d alphas = -bg, d out / d bg = 1 - alphas: elementwise products and sums over the pixels
+        alphas, bg = ctx.saved_tensors
+        b = bg.detach().float().reshape(-1)
+        g_al = -(g * b).sum(-1) if ctx.needs_input_grad[1] else None
+        g_bg = (g * (1.0 - alphas.detach().float())[..., None]).reshape(-1, b.numel()).sum(0).reshape(bg.shape).to(bg.dtype) if ctx.needs_input_grad[2] else None
+        return g, g_al, g_bg
 
 
 def algorithmic_bytes(G: int, G_v: int, D: int, P: int, channels: Optional[int] = None) -> int:
