@@ -474,6 +474,21 @@ int siu3r_quat_scale_to_cov6_bwd(const float* quats_wxyz, const float* scales, c
 int siu3r_sh_eval_bwd(const float* means, const float* campos3_dev, const float* sh, int ncoef, int degree, const float* g_rgb, float* g_sh, float* g_means,
                       float* g_campos3, int64_t G, void* stream);
 
+/* ---- photometric loss of splat refinement (csrc/photo_loss.hip): loss = (1 - lambda) * L1 + lambda * (1 - SSIM), value and gradient fused ----
+ * pred / target: fp32 images of V views x C channels x H x W pixels, read AS STORED through four ELEMENT strides (view, channel, row,
+ * column; host arrays of 4, >= 0), so that [V,C,H,W] and [V,H,W,C] are both consumed without a copy.  L1 = mean |pred - target| over all
+ * pixels; SSIM = metrics.ssim with an explicit data_range (separable 11-tap Gaussian window, sigma 1.5, k1 0.01, k2 0.03, per channel,
+ * variances clamped at 0) averaged over the valid region (H - 10) x (W - 10), then over channels and views.  lambda = 0 computes no SSIM,
+ * lambda = 1 no L1 (the term left out is reported as NaN); every other lambda needs H, W >= 11.
+ * grad_pred (or NULL): d loss / d pred in pred's layout (same strides; every pixel is written), for a loss gradient of 1; the subgradient
+ * of |x| at 0 and the gradient through a clamped variance are 0.
+ * partials: 2 * siu3r_photo_loss_partials(V, C, H, W) floats of workspace (one (L1, SSIM) pair of sums per workgroup); out: 3 floats on
+ * the device = (loss, L1, SSIM).  Deterministic: fixed-order sums, no atomics; two calls on the same input give the same bits. */
+int64_t siu3r_photo_loss_partials(int V, int C, int H, int W);
+int siu3r_photo_loss(const float* pred, const float* target, int V, int C, int H, int W, const int64_t* pred_strides,
+                     const int64_t* target_strides, float lambda, float data_range, float* grad_pred, float* partials, float* out,
+                     void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,140 @@
+"""Photometric losses on the GPU: the objective of splat refinement, (1 - lambda) * L1 + lambda * (1 - SSIM), as ONE fused HIP kernel
+(csrc/photo_loss.hip: value and gradient of all views in one launch) behind torch autograd.
+
+SSIM is `metrics.ssim` with an explicit data_range (separable 11-tap Gaussian window, sigma 1.5, per channel, variances clamped at 0,
+averaged over the valid (H - 10) x (W - 10) region, then over channels and views); L1 is the mean of |pred - target| over everything.
+Images are read as stored: [V, C, H, W] (the K2 render), [V, H, W, C] with channels_last=True (the gsplat seam), sliced views of either;
+only a layout the kernel's four strides cannot express (an expanded dimension of a differentiated `pred`) costs a `.contiguous()`.
+There is no CPU path and nothing here synchronises with the host."""
+from __future__ import annotations
+
+import ctypes as C
+from typing import Tuple
+
+import torch
+
+from . import _lib
+from ._lib import check
+from .ops import _gpu, _p, _stream
+
+WINDOW = 11  # the SSIM window; H and W must reach it wherever SSIM is computed
+
+
+def _as_vchw(x: torch.Tensor, channels_last: bool) -> torch.Tensor:
+    """a [V, C, H, W] VIEW of an image batch stored as [V,C,H,W] / [C,H,W] or, channels_last, [V,H,W,C] / [H,W,C]"""
+    if x.dim() == 3:
+        x = x.unsqueeze(0)
+    return x.permute(0, 3, 1, 2) if channels_last else x
+
+
+def _check(pred: torch.Tensor, target: torch.Tensor, need_ssim: bool, channels_last: bool):
+    for name, t in (("pred", pred), ("target", target)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name} must be a tensor, got {type(t).__name__}")
+    _gpu(pred, target)
+    if pred.dtype != torch.float32 or target.dtype != torch.float32:
+        raise ValueError(f"photometric losses take float32 images, got {pred.dtype} and {target.dtype}")
+    if pred.dim() not in (3, 4):
+        raise ValueError(f"images must be [V,C,H,W], [V,H,W,C] or one image without V, got {tuple(pred.shape)}")
+    if pred.shape != target.shape:
+        raise ValueError(f"pred {tuple(pred.shape)} and target {tuple(target.shape)} differ in shape")
+    if pred.device != target.device:
+        raise ValueError(f"pred is on {pred.device}, target on {target.device}")
+    if pred.numel() == 0:
+        raise ValueError(f"empty images {tuple(pred.shape)}")
+    H, W = (pred.shape[-3], pred.shape[-2]) if channels_last else (pred.shape[-2], pred.shape[-1])
+    if need_ssim and min(H, W) < WINDOW:
+        raise ValueError(f"SSIM needs at least {WINDOW} x {WINDOW} pixels, got {H} x {W}")
+
+
+def _launch(pred4: torch.Tensor, target4: torch.Tensor, lambda_dssim: float, data_range: float, want_grad: bool):
+    """One siu3r_photo_loss call on [V,C,H,W] views with arbitrary non-negative strides.  Returns (out [3] = loss, L1, SSIM; grad in
+    pred4's layout or None; partials [tiles, 2] = the per-workgroup (L1, SSIM) sums, view-major)."""
+    lib = _lib.lib()
+    V, Cn, H, W = pred4.shape
+    dev = pred4.device
+    n = int(lib.siu3r_photo_loss_partials(V, Cn, H, W))
+    partials = torch.empty((n, 2), dtype=torch.float32, device=dev)
+    out = torch.empty(3, dtype=torch.float32, device=dev)
+    grad = torch.empty_strided(tuple(pred4.shape), tuple(pred4.stride()), dtype=torch.float32, device=dev) if want_grad else None
+    ps, ts = (C.c_int64 * 4)(*pred4.stride()), (C.c_int64 * 4)(*target4.stride())
+    with torch.cuda.device(dev):
+        check(lib.siu3r_photo_loss(_p(pred4), _p(target4), V, Cn, H, W, ps, ts, float(lambda_dssim), float(data_range), _p(grad), _p(partials), _p(out),
+                                   _stream()))
+    return out, grad, partials
+
+
+def _expressible(x4: torch.Tensor, written: bool) -> torch.Tensor:
+    """strides the kernel takes: non-negative; a tensor whose layout also receives the gradient must not overlap itself (no expanded dimension)"""
+    if written and any(st == 0 and sz > 1 for st, sz in zip(x4.stride(), x4.shape)):
+        return x4.contiguous()
+    return x4
+
+
+class _PhotoLoss(torch.autograd.Function):
+    """The fused kernel: the forward already produces d loss / d pred for a loss gradient of 1, the backward is one multiply."""
+
+    @staticmethod
+    def forward(ctx, pred, target, lambda_dssim, data_range, channels_last):
+        p4 = _expressible(_as_vchw(pred.detach(), channels_last), True)
+        t4 = _as_vchw(target.detach(), channels_last)
+        out, grad, _ = _launch(p4, t4, lambda_dssim, data_range, True)
+        ctx.save_for_backward(grad)
+        ctx.channels_last, ctx.shape = channels_last, pred.shape
+        loss, l1_, ssim_ = out[0], out[1], out[2]
+        ctx.mark_non_differentiable(l1_, ssim_)
+        return loss, l1_, ssim_
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_loss, _g_l1, _g_ssim):
+        (grad,) = ctx.saved_tensors
+        g = grad * g_loss
+        if ctx.channels_last:
+            g = g.permute(0, 2, 3, 1)
+        return g.reshape(ctx.shape), None, None, None, None
+
+
+def _terms(pred, target, lambda_dssim, data_range, channels_last) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    lambda_dssim, data_range = float(lambda_dssim), float(data_range)
+    if not 0.0 <= lambda_dssim <= 1.0:
+        raise ValueError(f"lambda_dssim must lie in [0, 1], got {lambda_dssim}")
+    if not data_range > 0.0:
+        raise ValueError(f"data_range must be positive, got {data_range}")
+    _check(pred, target, lambda_dssim != 0.0, channels_last)
+    if torch.is_grad_enabled() and pred.requires_grad:
+        return _PhotoLoss.apply(pred, target, lambda_dssim, data_range, channels_last)
+    out, _, _ = _launch(_as_vchw(pred.detach(), channels_last), _as_vchw(target.detach(), channels_last), lambda_dssim, data_range, False)
+    return out[0], out[1], out[2]
+
+
+def photometric_loss(pred: torch.Tensor, target: torch.Tensor, lambda_dssim: float = 0.2, data_range: float = 1.0, channels_last: bool = False,
+                     return_terms: bool = False):
+    """(1 - lambda_dssim) * L1 + lambda_dssim * (1 - SSIM) of float32 GPU images [V,C,H,W] (channels_last: [V,H,W,C]; a single image may
+    drop V), as a 0-d tensor on the device.  Differentiable w.r.t. `pred` (the subgradient of |x| at 0 and the gradient through a clamped
+    variance are 0); `target` receives no gradient.  return_terms: (loss, L1, SSIM), the two terms detached; a term that lambda_dssim = 0
+    or 1 switches off is not computed and comes back as NaN.  Every lambda_dssim other than 0 needs H, W >= 11."""
+    loss, l1_, ssim_ = _terms(pred, target, lambda_dssim, data_range, channels_last)
+    return (loss, l1_, ssim_) if return_terms else loss
+
+
+def ssim(pred: torch.Tensor, target: torch.Tensor, data_range: float = 1.0, channels_last: bool = False, reduction: str = "mean") -> torch.Tensor:
+    """`metrics.ssim(..., data_range=data_range)` on the GPU: the mean over views and channels as a 0-d tensor (differentiable w.r.t. `pred`),
+    or with reduction="none" one value per view [V] (not differentiable)."""
+    if reduction not in ("mean", "none"):
+        raise ValueError(f'reduction must be "mean" or "none", got {reduction!r}')
+    if reduction == "mean":
+        if torch.is_grad_enabled() and isinstance(pred, torch.Tensor) and pred.requires_grad:
+            return 1.0 - photometric_loss(pred, target, 1.0, data_range, channels_last)
+        return _terms(pred, target, 1.0, data_range, channels_last)[2]
+    _check(pred, target, True, channels_last)
+    p4, t4 = _as_vchw(pred.detach(), channels_last), _as_vchw(target.detach(), channels_last)
+    _, _, partials = _launch(p4, t4, 1.0, float(data_range), False)
+    V, Cn, H, W = p4.shape
+    per_view = partials.view(V, -1, 2)[:, :, 1].sum(1, dtype=torch.float64) / float(Cn * (H - WINDOW + 1) * (W - WINDOW + 1))
+    return per_view.float()
+
+
+def l1(pred: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
+    """mean |pred - target| over everything as a 0-d device tensor (differentiable w.r.t. `pred`); any of the layouts above"""
+    return photometric_loss(pred, target, 0.0)

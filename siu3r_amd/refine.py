@@ -1,0 +1,95 @@
+"""Per-scene refinement: optimise the Gaussians themselves against posed target images (the second inference-time use of the HIP rasterizer
+backward; the first is pose_align.align_pose).  Every iteration is ONE multi-view K2 render (cuda_splatting.render_cuda), ONE fused photometric
+loss (losses.photometric_loss) and one backward; the optimiser is torch's Adam.  A caller whose views are unposed aligns them first
+(align_pose) and refines second."""
+from __future__ import annotations
+
+from typing import Dict, List, Optional, Sequence, Tuple
+
+import torch
+
+from . import raster
+from .cuda_splatting import render_cuda
+from .losses import photometric_loss
+
+FIELDS = ("means", "scales", "rotations", "opacities", "harmonics")
+# Adam steps per field, those of the 3DGS training recipe (Kerbl et al. 2023): position 1.6e-4 (there times the scene extent, and decayed),
+# scaling 5e-3, rotation 1e-3, opacity 5e-2, SH 2.5e-3 (there the higher bands at a twentieth)
+DEFAULT_LRS = {"means": 1.6e-4, "scales": 5e-3, "rotations": 1e-3, "opacities": 5e-2, "harmonics": 2.5e-3}
+_COV33 = (0, 1, 2, 1, 3, 4, 2, 4, 5)  # [G,6] upper triangle -> [G,3,3]
+
+
+def covariances_from(rotations_xyzw: torch.Tensor, scales: torch.Tensor) -> torch.Tensor:
+    """[G,3,3] covariances R diag(scales^2) R^T of RAW (x, y, z, w) quaternions (normalised inside the kernel), no further transform"""
+    cov6 = raster.quat_scale_to_cov6(torch.roll(rotations_xyzw, 1, dims=-1), scales)
+    return cov6[:, list(_COV33)].view(-1, 3, 3)
+
+
+def refine_gaussians(means, scales, rotations, opacities, harmonics, images, c2w, Kn, near, far, bg, iters: int = 200, lambda_dssim: float = 0.2,
+                     lrs: Optional[Dict[str, float]] = None, params: Sequence[str] = FIELDS, log_every: int = 1
+                     ) -> Tuple[Dict[str, torch.Tensor], List[float]]:
+    """means [G,3], scales [G,3], rotations [G,4], opacities [G], harmonics [G,3,n] (n = (deg+1)^2): what `Gaussians` carries, on the GPU.
+    images [V,3,H,W]: the posed target views; c2w [V,4,4] camera-to-world, Kn [V,3,3] (or [3,3]) normalised intrinsics, near / far floats
+    (or [V]), bg 3 floats: render_cuda's conventions.
+
+    `rotations` are the adapter's RAW quaternions in (x, y, z, w) order, as `Gaussians.rotations` holds them; the covariance is built from
+    their normalised form and `scales` with no further transform.  raster.quat_scale_to_cov6 takes (w, x, y, z): the reordering happens in
+    here, and the returned `rotations` are in the input's order again.
+
+    Optimised is the usual unconstrained parametrisation: means, log-scales, raw quaternions, logit opacities (the inputs clamped into
+    [1e-6, 1 - 1e-6] before the logit), SH coefficients; covariances are rebuilt from quaternions and scales every step.  `params` names the
+    fields that move; the others stay frozen, receive no gradient and are returned bit-identical.  One torch.optim.Adam with a parameter
+    group per field; `lrs` overrides DEFAULT_LRS per field.  iters = 0 moves nothing.
+
+    Returns ({"means", "scales", "rotations", "opacities", "harmonics", "covariances" [G,3,3]}: new tensors, the inputs are not modified;
+    the losses of the logged iterations: every `log_every`-th, each costing one host read; log_every = 0 reads nothing)."""
+    params = tuple(params)
+    for p in params:
+        if p not in FIELDS:
+            raise ValueError(f"params: unknown field {p!r} (one of {FIELDS})")
+    lr = dict(DEFAULT_LRS)
+    for k, v in (lrs or {}).items():
+        if k not in FIELDS:
+            raise ValueError(f"lrs: unknown field {k!r} (one of {FIELDS})")
+        lr[k] = float(v)
+    if int(iters) <= 0:
+        params = ()
+    dev = means.device
+    start = {"means": means, "scales": scales, "rotations": rotations, "opacities": opacities, "harmonics": harmonics}
+    start = {k: v.detach().float() for k, v in start.items()}
+    target = images.detach().float().to(dev)
+    V, _, H, W = target.shape
+    c2w = c2w.detach().float().to(dev)
+    Kn = Kn.detach().float().to(dev)
+    Kn = Kn[None].expand(V, 3, 3) if Kn.dim() == 2 else Kn
+    as_v = lambda x: x.detach().float().cpu().reshape(-1).expand(V) if isinstance(x, torch.Tensor) else torch.full((V,), float(x))
+    near_t, far_t = as_v(near), as_v(far)
+    bg_t = torch.tensor([[float(b) for b in bg]]).expand(V, 3)
+
+    # the free fields in their unconstrained form
+    to_param = {"means": lambda x: x.clone(), "scales": torch.log, "rotations": lambda x: x.clone(),
+                "opacities": lambda x: torch.logit(x.clamp(1e-6, 1 - 1e-6)), "harmonics": lambda x: x.clone()}
+    from_param = {"means": lambda x: x, "scales": torch.exp, "rotations": lambda x: x, "opacities": torch.sigmoid, "harmonics": lambda x: x}
+    free = {k: to_param[k](start[k]).requires_grad_(True) for k in FIELDS if k in params}
+    value = lambda k: from_param[k](free[k]) if k in free else start[k]
+    cov_moves = "scales" in free or "rotations" in free
+    cov6_of = lambda: raster.quat_scale_to_cov6(torch.roll(value("rotations"), 1, dims=-1), value("scales"))
+    cov6_fixed = None if cov_moves else cov6_of()
+
+    losses: List[float] = []
+    if free:
+        opt = torch.optim.Adam([{"params": [free[k]], "lr": lr[k]} for k in free], eps=1e-15, fused=True)
+        for it in range(int(iters)):
+            opt.zero_grad(set_to_none=True)
+            cov6 = cov6_of() if cov_moves else cov6_fixed
+            img, _ = render_cuda(c2w, Kn, near_t, far_t, (H, W), bg_t, value("means")[None].expand(V, -1, -1), cov6[None].expand(V, -1, -1),
+                                 value("harmonics")[None].expand(V, -1, -1, -1), value("opacities")[None].expand(V, -1))
+            loss = photometric_loss(img, target, lambda_dssim)
+            loss.backward()
+            opt.step()
+            if log_every and it % int(log_every) == 0:
+                losses.append(float(loss.detach()))
+    with torch.no_grad():
+        out = {k: (value(k).detach().clone() if k in free else start[k].clone()) for k in FIELDS}
+        out["covariances"] = covariances_from(out["rotations"], out["scales"])
+    return out, losses
