@@ -95,15 +95,10 @@ __global__ __launch_bounds__(256) void project_kernel(const Cam* __restrict__ ca
   const int lane_ = threadIdx.x & 63, wave_ = threadIdx.x >> 6;
   float sh[76];
   bool sh_loaded = false;
-  float m0 = 0.f, m1 = 0.f, m2 = 0.f, opacity = 0.f, sxx = 0.f, sxy = 0.f, sxz = 0.f, syy = 0.f, syz = 0.f, szz = 0.f;
+  float m[3] = {0.f, 0.f, 0.f}, opacity = 0.f, S[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   if (g < G) {
-    m0 = means[3 * g];
-    m1 = means[3 * g + 1];
-    m2 = means[3 * g + 2];
+    load_gaussian(means, cov, cov_stride, g, m, S);
     opacity = opac[g];
-    const float* cg = cov + (size_t)g * cov_stride;
-    const bool tri = cov_stride == 6;
-    sxx = cg[0]; sxy = cg[1]; sxz = cg[2]; syy = cg[tri ? 3 : 4]; syz = cg[tri ? 4 : 5]; szz = cg[tri ? 5 : 8];
   }
   for (int v = v_begin; v < v_end; ++v) {
   const Cam& c = cams[v];
@@ -114,48 +109,16 @@ __global__ __launch_bounds__(256) void project_kernel(const Cam* __restrict__ ca
     const float* V = c.w2c;
     int rx_i = 0, ry_i = 0, tx0 = 0, ty0 = 0, tx1 = 0, ty1 = 0;
     float mx = 0.f, my = 0.f, ca = 0.f, cb = 0.f, cc = 0.f;
-    const float tx = V[0] * m0 + V[1] * m1 + V[2] * m2 + V[3];
-    const float ty = V[4] * m0 + V[5] * m1 + V[6] * m2 + V[7];
-    const float tz = V[8] * m0 + V[9] * m1 + V[10] * m2 + V[11];
+    const float tx = V[0] * m[0] + V[1] * m[1] + V[2] * m[2] + V[3];
+    const float ty = V[4] * m[0] + V[5] * m[1] + V[6] * m[2] + V[7];
+    const float tz = V[8] * m[0] + V[9] * m[1] + V[10] * m[2] + V[11];
     const int gw = (c.width + TILE - 1) / TILE, gh = (c.height + TILE - 1) / TILE;
     do {
-      float fx, fy;
-      if (c.mode == 0) {
-        if (tz <= c.k2_znear_cull) break;
-        fx = c.width / (2.0f * c.tanfovx);
-        fy = c.height / (2.0f * c.tanfovy);
-      } else {
-        if (tz < c.near_plane || tz > c.far_plane) break;
-        fx = c.fx;
-        fy = c.fy;
-      }
-      float limx_pos, limx_neg, limy_pos, limy_neg;
-      if (c.mode == 0) {
-        limx_pos = limx_neg = 1.3f * c.tanfovx;
-        limy_pos = limy_neg = 1.3f * c.tanfovy;
-      } else {
-        const float tfx = 0.5f * c.width / fx, tfy = 0.5f * c.height / fy;
-        limx_pos = (c.width - c.cx) / fx + 0.3f * tfx;
-        limx_neg = c.cx / fx + 0.3f * tfx;
-        limy_pos = (c.height - c.cy) / fy + 0.3f * tfy;
-        limy_neg = c.cy / fy + 0.3f * tfy;
-      }
-      const float rz = 1.0f / tz;
-      const float txz = tx * rz, tyz = ty * rz;
-      const float cxz = fminf(limx_pos, fmaxf(-limx_neg, txz)), cyz = fminf(limy_pos, fmaxf(-limy_neg, tyz));
-      const float ctx = cxz * tz, cty = cyz * tz;
-      const float j00 = fx * rz, j02 = -(fx * ctx) * rz * rz, j11 = fy * rz, j12 = -(fy * cty) * rz * rz;
-      const float m00 = j00 * V[0] + j02 * V[8], m01 = j00 * V[1] + j02 * V[9], m02 = j00 * V[2] + j02 * V[10];
-      const float m10 = j11 * V[4] + j12 * V[8], m11 = j11 * V[5] + j12 * V[9], m12 = j11 * V[6] + j12 * V[10];
-      const float a0 = m00 * sxx + m01 * sxy + m02 * sxz, a1 = m00 * sxy + m01 * syy + m02 * syz, a2 = m00 * sxz + m01 * syz + m02 * szz;
-      const float b0 = m10 * sxx + m11 * sxy + m12 * sxz, b1 = m10 * sxy + m11 * syy + m12 * syz, b2 = m10 * sxz + m11 * syz + m12 * szz;
-      float c00 = a0 * m00 + a1 * m01 + a2 * m02;
-      const float c01 = a0 * m10 + a1 * m11 + a2 * m12;
-      float c11 = b0 * m10 + b1 * m11 + b2 * m12;
-      const float blur = c.mode == 0 ? c.dilation : c.eps2d;
-      c00 += blur;
-      c11 += blur;
-      const float det = c00 * c11 - c01 * c01;
+      if (c.mode == 0 ? (tz <= c.k2_znear_cull) : (tz < c.near_plane || tz > c.far_plane)) break;
+      const Lens lens = c.mode == 0 ? lens_k2(c) : lens_k3(c);
+      const float fx = lens.fx, fy = lens.fy;
+      const Cov2D p = project_cov2d(lens, V, tx, ty, tz, S);
+      const float txz = p.txz, tyz = p.tyz, c00 = p.c00, c01 = p.c01, c11 = p.c11, det = p.det;
       if (c.mode == 0 ? (det == 0.0f) : (det <= 0.0f)) break;
       const float det_inv = 1.0f / det;
       ca = c11 * det_inv;
@@ -163,9 +126,9 @@ __global__ __launch_bounds__(256) void project_kernel(const Cam* __restrict__ ca
       cc = c00 * det_inv;
       if (c.mode == 0) {
         const float* P = c.proj;
-        const float hx = P[0] * m0 + P[1] * m1 + P[2] * m2 + P[3];
-        const float hy = P[4] * m0 + P[5] * m1 + P[6] * m2 + P[7];
-        const float hw = P[12] * m0 + P[13] * m1 + P[14] * m2 + P[15];
+        const float hx = P[0] * m[0] + P[1] * m[1] + P[2] * m[2] + P[3];
+        const float hy = P[4] * m[0] + P[5] * m[1] + P[6] * m[2] + P[7];
+        const float hw = P[12] * m[0] + P[13] * m[1] + P[14] * m[2] + P[15];
         const float pw = 1.0f / (hw + 0.0000001f);
         mx = ((hx * pw + 1.0f) * c.width - 1.0f) * 0.5f;
         my = ((hy * pw + 1.0f) * c.height - 1.0f) * 0.5f;
@@ -225,7 +188,7 @@ __global__ __launch_bounds__(256) void project_kernel(const Cam* __restrict__ ca
       rp[2] = make_float4(colors[3 * g], colors[3 * g + 1], colors[3 * g + 2], 0.f);
     }
     if (valid && c.mode == 0 && c.sh_degree >= 0) {
-      const float dx = m0 - c.campos[0], dy = m1 - c.campos[1], dz = m2 - c.campos[2];
+      const float dx = m[0] - c.campos[0], dy = m[1] - c.campos[1], dz = m[2] - c.campos[2];
       const float inv = 1.0f / sqrtf(dx * dx + dy * dy + dz * dz);
       const float x = dx * inv, y = dy * inv, z = dz * inv;
       const int deg = c.sh_degree;
@@ -726,22 +689,7 @@ __global__ __launch_bounds__(256) void composite_rgb_kernel(const Cam* __restric
           *(float4*)s_a[off] = r0;
           *(float4*)s_co[off] = r1;
           *(float4*)s_c[off] = r2;
-          // footprint box: alpha >= alpha_min  =>  sigma <= L = ln(opacity / alpha_min)  =>  |dx| <= sqrt(2 L cov_xx), cov = conic^-1.
-          // Padded by 1 % + 0.05 px (the exact per-pixel tests below still decide; the box only has to be conservative)
-          int mk = 15;  // NaN / degenerate conics: no culling, the exact tests decide
-          const float L = __logf(r1.w / alpha_min);
-          const float det = conic_det(r1.x, r1.y, r1.z);
-          if (L <= 0.f) {
-            mk = 0;  // opacity below alpha_min: alpha = min(alpha_max, opacity * exp(<= 0)) can never reach it
-          } else if (det > 0.f) {
-            // (K3: pixel centres sit half a pixel further: the box grows by that much)
-            const float ex = sqrtf(2.f * L * r1.z / det) * 1.01f + (K3 ? 0.55f : 0.05f), ey = sqrtf(2.f * L * r1.x / det) * 1.01f + (K3 ? 0.55f : 0.05f);
-            const float x0 = r0.x - ex - tile_x0, x1 = r0.x + ex - tile_x0, y0 = r0.y - ey - tile_y0, y1 = r0.y + ey - tile_y0;
-            const int cx = (x0 <= 7.f && x1 >= 0.f ? 1 : 0) | (x0 <= 15.f && x1 >= 8.f ? 2 : 0);
-            const int cy = (y0 <= 7.f && y1 >= 0.f ? 1 : 0) | (y0 <= 15.f && y1 >= 8.f ? 2 : 0);
-            mk = ((cy & 1) ? cx : 0) | ((cy & 2) ? (cx << 2) : 0);
-          }
-          s_m[off] = mk;
+          s_m[off] = quadrant_mask<K3>(r0, r1, alpha_min, tile_x0, tile_y0);
         }
       }
       staged = run;
@@ -750,7 +698,8 @@ __global__ __launch_bounds__(256) void composite_rgb_kernel(const Cam* __restric
     }
     if (staged == 0) break;
     // this wave's own list (order kept) of the staged survivors that can reach its quadrant: ballot + prefix popcount again, wave-local
-    // (LDS operations of one wave complete in order: no barrier)
+    // (no workgroup barrier: only this wave reads its list.  The wave barrier below the loop keeps the compiler from moving the walk's
+    // reads above these stores; the hardware completes one wave's LDS operations in order)
     int nq = 0;
     for (int b = 0; b < ((SIU3R_COMP_DBG & 2) ? 0 : staged); b += 64) {
       const int i = b + lane;
@@ -759,6 +708,7 @@ __global__ __launch_bounds__(256) void composite_rgb_kernel(const Cam* __restric
       if (hit) s_list[wave][nq + __popcll(mh & ((1ull << lane) - 1ull))] = (unsigned short)i;
       nq += __popcll(mh);
     }
+    __builtin_amdgcn_wave_barrier();
     // The walk.  Rounds 2-5 evaluated one entry per iteration behind four nested early-outs (power > 0, x < -87 inside the exponential,
     // alpha < alpha_min, saturation): ~55 vector + ~35 scalar / branch instructions per (wave, entry), nine of the vector ones register
     // moves that rotated the software prefetch, and the early-outs almost never fire wave-wide (a listed entry nearly always has SOME
@@ -795,7 +745,8 @@ __global__ __launch_bounds__(256) void composite_rgb_kernel(const Cam* __restric
     };
     // (two 16-bit indices per 32-bit read: the lists start 4-byte aligned and pairs start at even positions)
     auto pair_idx = [&](int i, int& ja, int& jb) {
-      const unsigned u = i < nq ? *(const unsigned*)(lst + i) : 0u;
+      unsigned u = 0u;
+      if (i < nq) __builtin_memcpy(&u, (const unsigned short*)__builtin_assume_aligned(lst + i, 4), 4);  // (alias-safe: the list is filled as 16-bit stores)
       ja = (int)(u & 0xffffu);
       jb = i + 1 < nq ? (int)(u >> 16) : 0;
     };

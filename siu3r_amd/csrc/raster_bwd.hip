@@ -11,7 +11,7 @@
 //                   an LDS slot of the staged entry; after the slice the workgroup adds every non-zero slot to global memory: one float atomic per
 //                   (tile, Gaussian, term).
 //   projection bwd  one thread per Gaussian, looping over the call's views like project_kernel: per-Gaussian gradients are plain stores.
-//                   The six pose terms of a view are summed per workgroup into a partial row; pose_reduce_kernel sums the rows.
+//                   The six pose terms of a view are summed per workgroup into a partial row; rows_reduce_kernel<6, 6> sums the rows.
 // The gradient is that of the function the forward computes, on the branch it took: culling, tile rects, the alpha_min cut-off,
 // saturation and the alpha_max clamp are held constant (no gradient through a clamped alpha); the limx / limy clamp of the Jacobian
 // passes no gradient to the clamped component; a colour clamped at 0 passes none to its SH coefficients.
@@ -111,20 +111,7 @@ __global__ __launch_bounds__(256) void composite_rgb_bwd_kernel(const Cam* __res
       *(float4*)s_a[off] = r0;
       *(float4*)s_co[off] = r1;
       *(float4*)s_c[off] = r2;
-      // the forward's footprint box, the same expression (composite_rgb_kernel): a wave skips exactly the entries the forward's wave skipped
-      int mk = 15;
-      const float L = __logf(r1.w / alpha_min);
-      const float det = conic_det(r1.x, r1.y, r1.z);
-      if (L <= 0.f) {
-        mk = 0;
-      } else if (det > 0.f) {
-        const float ex = sqrtf(2.f * L * r1.z / det) * 1.01f + (K3 ? 0.55f : 0.05f), ey = sqrtf(2.f * L * r1.x / det) * 1.01f + (K3 ? 0.55f : 0.05f);
-        const float x0 = r0.x - ex - tile_x0, x1 = r0.x + ex - tile_x0, y0 = r0.y - ey - tile_y0, y1 = r0.y + ey - tile_y0;
-        const int cx = (x0 <= 7.f && x1 >= 0.f ? 1 : 0) | (x0 <= 15.f && x1 >= 8.f ? 2 : 0);
-        const int cy = (y0 <= 7.f && y1 >= 0.f ? 1 : 0) | (y0 <= 15.f && y1 >= 8.f ? 2 : 0);
-        mk = ((cy & 1) ? cx : 0) | ((cy & 2) ? (cx << 2) : 0);
-      }
-      s_m[off] = mk;
+      s_m[off] = quadrant_mask<K3>(r0, r1, alpha_min, tile_x0, tile_y0);  // the forward's: a wave skips exactly the entries the forward's wave skipped
 #pragma unroll
       for (int k = 0; k < GR_N; ++k) s_g[off][k] = 0.f;
     }
@@ -204,19 +191,11 @@ __global__ __launch_bounds__(256) void project_bwd_kernel(const Cam* __restrict_
                                                           const int32_t* __restrict__ rect, const float* __restrict__ grad, float* __restrict__ g_means,
                                                           float* __restrict__ g_cov, float* __restrict__ g_opac, float* __restrict__ g_colors,
                                                           float* __restrict__ g_mean2d, float* __restrict__ pose_part) {
-  __shared__ float s_pose[4][6];
   const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const bool live = g < G;
   float m[3] = {0.f, 0.f, 0.f}, S[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   const bool tri = cov_stride == 6;
-  if (live) {
-    m[0] = means[3 * g];
-    m[1] = means[3 * g + 1];
-    m[2] = means[3 * g + 2];
-    const float* cg = cov + (size_t)g * cov_stride;
-    S[0] = cg[0]; S[1] = cg[1]; S[2] = cg[2]; S[3] = cg[tri ? 3 : 4]; S[4] = cg[tri ? 4 : 5]; S[5] = cg[tri ? 5 : 8];
-  }
+  if (live) load_gaussian(means, cov, cov_stride, g, m, S);
   const float* shp = colors + (size_t)(live ? g : 0) * channels * 3;
   auto coef = [&](int k, int ch) { return sh_planar ? shp[ch * 25 + k] : shp[k * 3 + ch]; };
   float gm[3] = {0.f, 0.f, 0.f}, gS[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, gop = 0.f, gsh[75];
@@ -239,55 +218,25 @@ __global__ __launch_bounds__(256) void project_bwd_kernel(const Cam* __restrict_
       const float tx = W[0] * m[0] + W[1] * m[1] + W[2] * m[2] + W[3];
       const float ty = W[4] * m[0] + W[5] * m[1] + W[6] * m[2] + W[7];
       const float tz = W[8] * m[0] + W[9] * m[1] + W[10] * m[2] + W[11];
-      const float fx = c.width / (2.0f * c.tanfovx), fy = c.height / (2.0f * c.tanfovy);
-      const float limx = 1.3f * c.tanfovx, limy = 1.3f * c.tanfovy;
-      const float rz = 1.0f / tz;
-      const float txz = tx * rz, tyz = ty * rz;
-      const float cxz = fminf(limx, fmaxf(-limx, txz)), cyz = fminf(limy, fmaxf(-limy, tyz));
-      const float ctx = cxz * tz, cty = cyz * tz;
-      const float j00 = fx * rz, j02 = -(fx * ctx) * rz * rz, j11 = fy * rz, j12 = -(fy * cty) * rz * rz;
-      const float t0[3] = {j00 * W[0] + j02 * W[8], j00 * W[1] + j02 * W[9], j00 * W[2] + j02 * W[10]};
-      const float t1[3] = {j11 * W[4] + j12 * W[8], j11 * W[5] + j12 * W[9], j11 * W[6] + j12 * W[10]};
-      // Sigma t0, Sigma t1 (Sigma symmetric from the six entries)
-      const float a[3] = {t0[0] * S[0] + t0[1] * S[1] + t0[2] * S[2], t0[0] * S[1] + t0[1] * S[3] + t0[2] * S[4], t0[0] * S[2] + t0[1] * S[4] + t0[2] * S[5]};
-      const float b[3] = {t1[0] * S[0] + t1[1] * S[1] + t1[2] * S[2], t1[0] * S[1] + t1[1] * S[3] + t1[2] * S[4], t1[0] * S[2] + t1[1] * S[4] + t1[2] * S[5]};
-      const float c00 = a[0] * t0[0] + a[1] * t0[1] + a[2] * t0[2] + c.dilation;
-      const float c01 = a[0] * t1[0] + a[1] * t1[1] + a[2] * t1[2];
-      const float c11 = b[0] * t1[0] + b[1] * t1[1] + b[2] * t1[2] + c.dilation;
-      const float det = c00 * c11 - c01 * c01, rdet = 1.0f / det;
-      const float ca = c11 * rdet, cb = -c01 * rdet, cc = c00 * rdet;
-      // conic inverse
-      const float dLddet = -(gr[GR_CA] * ca + gr[GR_CB] * cb + gr[GR_CC] * cc) * rdet;
-      const float d00 = gr[GR_CC] * rdet + dLddet * c11, d11 = gr[GR_CA] * rdet + dLddet * c00, d01 = -gr[GR_CB] * rdet - 2.0f * dLddet * c01;
-      // 2-D covariance = T Sigma T^T, T = J W (rows t0, t1)
-      float dt0[3], dt1[3];
-#pragma unroll
-      for (int i = 0; i < 3; ++i) {
-        dt0[i] = 2.0f * d00 * a[i] + d01 * b[i];
-        dt1[i] = 2.0f * d11 * b[i] + d01 * a[i];
-      }
-      gS[0] += d00 * t0[0] * t0[0] + d01 * t0[0] * t1[0] + d11 * t1[0] * t1[0];
-      gS[3] += d00 * t0[1] * t0[1] + d01 * t0[1] * t1[1] + d11 * t1[1] * t1[1];
-      gS[5] += d00 * t0[2] * t0[2] + d01 * t0[2] * t1[2] + d11 * t1[2] * t1[2];
-      gS[1] += 2.0f * d00 * t0[0] * t0[1] + d01 * (t0[0] * t1[1] + t0[1] * t1[0]) + 2.0f * d11 * t1[0] * t1[1];
-      gS[2] += 2.0f * d00 * t0[0] * t0[2] + d01 * (t0[0] * t1[2] + t0[2] * t1[0]) + 2.0f * d11 * t1[0] * t1[2];
-      gS[4] += 2.0f * d00 * t0[1] * t0[2] + d01 * (t0[1] * t1[2] + t0[2] * t1[1]) + 2.0f * d11 * t1[1] * t1[2];
+      const Lens lens = lens_k2(c);
+      const float fx = lens.fx, fy = lens.fy;
+      const Cov2D p = project_cov2d(lens, W, tx, ty, tz, S);
+      const Cov2DGrad q = project_cov2d_bwd(p, W, gr[GR_CA], gr[GR_CB], gr[GR_CC], gS);
       const float W0[3] = {W[0], W[1], W[2]}, W1[3] = {W[4], W[5], W[6]}, W2[3] = {W[8], W[9], W[10]};
-      const float dj00 = dt0[0] * W0[0] + dt0[1] * W0[1] + dt0[2] * W0[2], dj02 = dt0[0] * W2[0] + dt0[1] * W2[1] + dt0[2] * W2[2];
-      const float dj11 = dt1[0] * W1[0] + dt1[1] * W1[1] + dt1[2] * W1[2], dj12 = dt1[0] * W2[0] + dt1[1] * W2[1] + dt1[2] * W2[2];
       // d loss / d W through the covariance only (rows), for the rotation part of the pose gradient
       float GW[3][3];
 #pragma unroll
       for (int i = 0; i < 3; ++i) {
-        GW[0][i] = j00 * dt0[i];
-        GW[1][i] = j11 * dt1[i];
-        GW[2][i] = j02 * dt0[i] + j12 * dt1[i];
+        GW[0][i] = p.j00 * q.dt0[i];
+        GW[1][i] = p.j11 * q.dt1[i];
+        GW[2][i] = p.j02 * q.dt0[i] + p.j12 * q.dt1[i];
       }
       // Jacobian -> camera-space point (the clamp of txz / tyz passes nothing to the clamped component)
-      float drz = dj00 * fx + dj11 * fy - 2.0f * fx * ctx * rz * dj02 - 2.0f * fy * cty * rz * dj12;
-      const float dctx = -fx * rz * rz * dj02, dcty = -fy * rz * rz * dj12;
-      float dtz = dctx * cxz + dcty * cyz + gr[GR_Z];
-      const float dtxz = (cxz == txz) ? dctx * tz : 0.f, dtyz = (cyz == tyz) ? dcty * tz : 0.f;
+      const float rz = p.rz;
+      float drz = q.dj00 * fx + q.dj11 * fy - 2.0f * fx * p.ctx * rz * q.dj02 - 2.0f * fy * p.cty * rz * q.dj12;
+      const float dctx = -fx * rz * rz * q.dj02, dcty = -fy * rz * rz * q.dj12;
+      float dtz = dctx * p.cxz + dcty * p.cyz + gr[GR_Z];
+      const float dtxz = (p.cxz == p.txz) ? dctx * tz : 0.f, dtyz = (p.cyz == p.tyz) ? dcty * tz : 0.f;
       const float dtx = dtxz * rz, dty = dtyz * rz;
       drz += dtxz * tx + dtyz * ty;
       dtz += -drz * rz * rz;
@@ -338,54 +287,18 @@ __global__ __launch_bounds__(256) void project_bwd_kernel(const Cam* __restrict_
         gsh[1] += gcol[1];
         gsh[2] += gcol[2];
       } else {
-        const float ddx = m[0] - c.campos[0], ddy = m[1] - c.campos[1], ddz = m[2] - c.campos[2];
-        const float len = sqrtf(ddx * ddx + ddy * ddy + ddz * ddz), inv = 1.0f / len;
-        const float x = ddx * inv, y = ddy * inv, z = ddz * inv;
-        const int deg = c.sh_degree;
-        const bool band4 = c.sh_band4 != 0;
-        // which channels the +0.5 / clamp-at-0 left alive
-        float rsum[3] = {0.5f, 0.5f, 0.5f};
-        sh_basis(x, y, z, deg, band4, [&](int k, Dual bk) {
-#pragma unroll
-          for (int ch = 0; ch < 3; ++ch) rsum[ch] += bk.v * coef(k, ch);
-        });
-        float gl[3];
-#pragma unroll
-        for (int ch = 0; ch < 3; ++ch) gl[ch] = rsum[ch] < 0.0f ? 0.0f : gcol[ch];
-        float gd[3] = {0.f, 0.f, 0.f};
-        sh_basis(x, y, z, deg, band4, [&](int k, Dual bk) {
-          float s = 0.f;
-#pragma unroll
-          for (int ch = 0; ch < 3; ++ch) {
-            gsh[3 * k + ch] += bk.v * gl[ch];
-            s += gl[ch] * coef(k, ch);
-          }
-          gd[0] += s * bk.x;
-          gd[1] += s * bk.y;
-          gd[2] += s * bk.z;
-        });
-        // unit direction (m - campos) / |m - campos|
-        const float dd = gd[0] * x + gd[1] * y + gd[2] * z;
-        gm[0] += (gd[0] - x * dd) * inv;
-        gm[1] += (gd[1] - y * dd) * inv;
-        gm[2] += (gd[2] - z * dd) * inv;
+        const float3 gdm = sh_color_bwd(view_dir(m, c.campos), c.sh_degree, c.sh_band4 != 0, gcol, coef,
+                                        [&](int k, int ch, float gv) { gsh[3 * k + ch] += gv; });
+        gm[0] += gdm.x;
+        gm[1] += gdm.y;
+        gm[2] += gdm.z;
       }
     }
-    if (pose_part) {  // (uniform: every thread of the workgroup runs every view)
-#pragma unroll
-      for (int k = 0; k < 6; ++k) {
-        const float s = wave_sum(dpose[k]);
-        if (lane == 0) s_pose[wave][k] = s;
-      }
-      __syncthreads();
-      if (threadIdx.x < 6) {
-        const int k = threadIdx.x;
-        pose_part[((int64_t)blockIdx.x * V + v) * 6 + k] = s_pose[0][k] + s_pose[1][k] + s_pose[2][k] + s_pose[3][k];
-      }
-      __syncthreads();
-    }
+    // (uniform: every thread of the workgroup runs every view)
+    if (pose_part) block_sum_row<6>(dpose, pose_part + ((int64_t)blockIdx.x * V + v) * 6);
   }
   if (!live) return;
+  // (kept in the kernel, in this form: as a shared function the [3,3] branch compiles to narrower stores and measured 1.3 % slower)
   g_means[3 * g] = gm[0];
   g_means[3 * g + 1] = gm[1];
   g_means[3 * g + 2] = gm[2];
@@ -410,28 +323,25 @@ __global__ __launch_bounds__(256) void project_bwd_kernel(const Cam* __restrict_
   }
 }
 
-// pose_part [nblk, V, 6] -> g_pose [V, 6]: one workgroup per view
-__global__ __launch_bounds__(256) void pose_reduce_kernel(int V, int64_t nblk, const float* __restrict__ pose_part, float* __restrict__ g_pose) {
-  __shared__ float s[4][6];
-  const int v = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  float acc[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-  for (int64_t b = threadIdx.x; b < nblk; b += 256)
-#pragma unroll
-    for (int k = 0; k < 6; ++k) acc[k] += pose_part[(b * V + v) * 6 + k];
-#pragma unroll
-  for (int k = 0; k < 6; ++k) {
-    const float t = wave_sum(acc[k]);
-    if (lane == 0) s[wave][k] = t;
+// the launcher body of both composite backwards (K3: no depth)
+template <bool K3>
+int composite_rgb_bwd(const char* who, const siu3r_raster_cam* cams_host, int V, const void* cams_dev, int64_t G, const int32_t* bin_start, const void* entries,
+                      int64_t cap_e, const float* rec, const float* image, const float* depth, const float* alpha, const float* g_image, const float* g_depth,
+                      const float* g_alpha, float* grad, void* stream) {
+  if (int rc = check_views(cams_host, V, K3 ? 1 : 0, who)) return rc;
+  SIU3R_CHECK(cams_dev && bin_start && image && alpha && g_image && g_alpha && (K3 || (depth && g_depth)) && (G == 0 || (entries && rec && grad)),
+              "%s: null pointer", who);
+  SIU3R_CHECK(G >= 0 && G < (1ll << 31) && cap_e > 0, "%s: bad sizes", who);
+  hipStream_t s = (hipStream_t)stream;
+  if (G == 0) return 0;
+  if (hipMemsetAsync(grad, 0, sizeof(float) * GR_N * (size_t)V * G, s) != hipSuccess) {
+    siu3r_set_error("%s: memset failed", who);
+    return 2;
   }
-  __syncthreads();
-  if (threadIdx.x < 6) g_pose[v * 6 + threadIdx.x] = s[0][threadIdx.x] + s[1][threadIdx.x] + s[2][threadIdx.x] + s[3][threadIdx.x];
-}
-
-int check_k2_views(const Cam* cams, int V, const char* who) {
-  SIU3R_CHECK(cams && V >= 1 && V <= 65535, "%s: bad view array (V = %d)", who, V);
-  for (int v = 0; v < V; ++v)
-    SIU3R_CHECK(cams[v].mode == 0 && cams[v].width == cams[0].width && cams[v].height == cams[0].height && cams[v].width > 0 && cams[v].height > 0,
-                "%s: the backward covers the 3DGS family (mode 0) with one frame size per call", who);
+  const Geo geo = make_geo(cams_host[0].width, cams_host[0].height);
+  hipLaunchKernelGGL(composite_rgb_bwd_kernel<K3>, dim3(geo.T, V), dim3(256), 0, s, (const Cam*)cams_dev, geo, bin_start, (const uint2*)entries, cap_e, rec, G,
+                     image, depth, alpha, g_image, g_depth, g_alpha, grad);
+  SIU3R_LAUNCH_CHECK(who);
   return 0;
 }
 
@@ -441,51 +351,22 @@ extern "C" int siu3r_raster_composite_rgb_bwd(const siu3r_raster_cam* cams_host,
                                               const void* entries, int64_t cap_e, const float* rec, const float* image, const float* depth,
                                               const float* alpha, const float* g_image, const float* g_depth, const float* g_alpha, float* grad,
                                               void* stream) {
-  if (int rc = check_k2_views(cams_host, V, "raster_composite_rgb_bwd")) return rc;
-  SIU3R_CHECK(cams_dev && bin_start && image && depth && alpha && g_image && g_depth && g_alpha && (G == 0 || (entries && rec && grad)),
-              "raster_composite_rgb_bwd: null pointer");
-  SIU3R_CHECK(G >= 0 && G < (1ll << 31) && cap_e > 0, "raster_composite_rgb_bwd: bad sizes");
-  hipStream_t s = (hipStream_t)stream;
-  if (G == 0) return 0;
-  if (hipMemsetAsync(grad, 0, sizeof(float) * GR_N * (size_t)V * G, s) != hipSuccess) {
-    siu3r_set_error("raster_composite_rgb_bwd: memset failed");
-    return 2;
-  }
-  const Geo geo = make_geo(cams_host[0].width, cams_host[0].height);
-  hipLaunchKernelGGL(composite_rgb_bwd_kernel<false>, dim3(geo.T, V), dim3(256), 0, s, (const Cam*)cams_dev, geo, bin_start, (const uint2*)entries, cap_e, rec, G,
-                     image, depth, alpha, g_image, g_depth, g_alpha, grad);
-  SIU3R_LAUNCH_CHECK("siu3r_raster_composite_rgb_bwd");
-  return 0;
+  return composite_rgb_bwd<false>("siu3r_raster_composite_rgb_bwd", cams_host, V, cams_dev, G, bin_start, entries, cap_e, rec, image, depth, alpha, g_image, g_depth,
+                                  g_alpha, grad, stream);
 }
 
 extern "C" int siu3r_raster_composite_rgb_bwd_k3(const siu3r_raster_cam* cams_host, int V, const void* cams_dev, int64_t G, const int32_t* bin_start,
                                                  const void* entries, int64_t cap_e, const float* rec, const float* colors, const float* alphas,
                                                  const float* g_colors, const float* g_alphas, float* grad, void* stream) {
-  SIU3R_CHECK(cams_host && V >= 1 && V <= 65535, "raster_composite_rgb_bwd_k3: bad view array (V = %d)", V);
-  for (int v = 0; v < V; ++v)
-    SIU3R_CHECK(cams_host[v].mode == 1 && cams_host[v].width == cams_host[0].width && cams_host[v].height == cams_host[0].height && cams_host[v].width > 0 &&
-                    cams_host[v].height > 0,
-                "raster_composite_rgb_bwd_k3: the gsplat family (mode 1) with one frame size per call");
-  SIU3R_CHECK(cams_dev && bin_start && colors && alphas && g_colors && g_alphas && (G == 0 || (entries && rec && grad)), "raster_composite_rgb_bwd_k3: null pointer");
-  SIU3R_CHECK(G >= 0 && G < (1ll << 31) && cap_e > 0, "raster_composite_rgb_bwd_k3: bad sizes");
-  hipStream_t s = (hipStream_t)stream;
-  if (G == 0) return 0;
-  if (hipMemsetAsync(grad, 0, sizeof(float) * GR_N * (size_t)V * G, s) != hipSuccess) {
-    siu3r_set_error("raster_composite_rgb_bwd_k3: memset failed");
-    return 2;
-  }
-  const Geo geo = make_geo(cams_host[0].width, cams_host[0].height);
-  hipLaunchKernelGGL(composite_rgb_bwd_kernel<true>, dim3(geo.T, V), dim3(256), 0, s, (const Cam*)cams_dev, geo, bin_start, (const uint2*)entries, cap_e, rec, G,
-                     colors, (const float*)nullptr, alphas, g_colors, (const float*)nullptr, g_alphas, grad);
-  SIU3R_LAUNCH_CHECK("siu3r_raster_composite_rgb_bwd_k3");
-  return 0;
+  return composite_rgb_bwd<true>("siu3r_raster_composite_rgb_bwd_k3", cams_host, V, cams_dev, G, bin_start, entries, cap_e, rec, colors, nullptr, alphas, g_colors,
+                                 nullptr, g_alphas, grad, stream);
 }
 
 extern "C" int siu3r_raster_project_bwd(const siu3r_raster_cam* cams_host, int V, const void* cams_dev, int64_t G, const float* means, const float* cov,
                                         int cov_stride, const float* opacities, const float* colors, int channels, int sh_planar, const int32_t* rect,
                                         const float* grad, float* g_means, float* g_cov, float* g_opacities, float* g_colors, float* g_mean2d,
                                         float* pose_part, void* stream) {
-  if (int rc = check_k2_views(cams_host, V, "raster_project_bwd")) return rc;
+  if (int rc = check_views(cams_host, V, 0, "raster_project_bwd")) return rc;
   SIU3R_CHECK(G >= 0 && G < (1ll << 31), "raster_project_bwd: G = %ld out of range", (long)G);
   SIU3R_CHECK(cams_dev && (G == 0 || (means && cov && opacities && colors && rect && grad && g_means && g_cov && g_opacities && g_colors)),
               "raster_project_bwd: null pointer");
@@ -507,7 +388,7 @@ extern "C" int64_t siu3r_raster_pose_partial_rows(int64_t G) { return G > 0 ? cd
 
 extern "C" int siu3r_raster_pose_reduce(int V, int64_t nrows, const float* pose_part, float* g_pose, void* stream) {
   SIU3R_CHECK(V >= 1 && V <= 65535 && nrows >= 0 && g_pose && (nrows == 0 || pose_part), "raster_pose_reduce: bad arguments");
-  hipLaunchKernelGGL(pose_reduce_kernel, dim3(V), dim3(256), 0, (hipStream_t)stream, V, nrows, pose_part, g_pose);
+  hipLaunchKernelGGL((rows_reduce_kernel<6, 6>), dim3(V), dim3(256), 0, (hipStream_t)stream, V, nrows, pose_part, g_pose);
   SIU3R_LAUNCH_CHECK("siu3r_raster_pose_reduce");
   return 0;
 }

@@ -17,7 +17,7 @@
 //                        32 consecutive channels = two 128-byte row segments).
 //                   The upstream gradient rows are re-read from L2 for both products (the operand choice).
 //   projection bwd  one thread per Gaussian, looping over the views: per-Gaussian gradients are plain stores, the 12 terms of d loss / d
-//                   [R | t] of a view are summed per workgroup into a partial row that viewmat_reduce_kernel sums.
+//                   [R | t] of a view are summed per workgroup into a partial row that rows_reduce_kernel<12, 16> sums.
 // The gradient is that of the function the forward computes, on the branch it took: near / far culling, det <= 0, the radius and
 // radius_clip, tile rects and list membership, the sigma < 0 skip, the alpha_min cut-off, saturation and the alpha_max clamp are held
 // constant; the Jacobian clamp passes no gradient to the clamped component; a colour clamped at 0 passes none to its SH coefficients.
@@ -226,19 +226,11 @@ __global__ __launch_bounds__(256) void project_bwd_k3_kernel(const Cam* __restri
                                                              const float* __restrict__ cov, int cov_stride, const int32_t* __restrict__ rect,
                                                              const float* __restrict__ grad, float* __restrict__ g_means, float* __restrict__ g_cov,
                                                              float* __restrict__ g_opac, float* __restrict__ g_colors, float* __restrict__ pose_part) {
-  __shared__ float s_pose[4][12];
   const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const bool live = g < G;
   float m[3] = {0.f, 0.f, 0.f}, S[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   const bool tri = cov_stride == 6;
-  if (live) {
-    m[0] = means[3 * g];
-    m[1] = means[3 * g + 1];
-    m[2] = means[3 * g + 2];
-    const float* cg = cov + (size_t)g * cov_stride;
-    S[0] = cg[0]; S[1] = cg[1]; S[2] = cg[2]; S[3] = cg[tri ? 3 : 4]; S[4] = cg[tri ? 4 : 5]; S[5] = cg[tri ? 5 : 8];
-  }
+  if (live) load_gaussian(means, cov, cov_stride, g, m, S);
   float gm[3] = {0.f, 0.f, 0.f}, gS[6] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f}, gop = 0.f, gcol[3] = {0.f, 0.f, 0.f};
   for (int v = 0; v < V; ++v) {
     const Cam& c = cams[v];
@@ -255,48 +247,17 @@ __global__ __launch_bounds__(256) void project_bwd_k3_kernel(const Cam* __restri
       const float tx = W[0] * m[0] + W[1] * m[1] + W[2] * m[2] + W[3];
       const float ty = W[4] * m[0] + W[5] * m[1] + W[6] * m[2] + W[7];
       const float tz = W[8] * m[0] + W[9] * m[1] + W[10] * m[2] + W[11];
-      const float fx = c.fx, fy = c.fy;
-      const float tfx = 0.5f * c.width / fx, tfy = 0.5f * c.height / fy;
-      const float limx_pos = (c.width - c.cx) / fx + 0.3f * tfx, limx_neg = c.cx / fx + 0.3f * tfx;
-      const float limy_pos = (c.height - c.cy) / fy + 0.3f * tfy, limy_neg = c.cy / fy + 0.3f * tfy;
-      const float rz = 1.0f / tz;
-      const float txz = tx * rz, tyz = ty * rz;
-      const float cxz = fminf(limx_pos, fmaxf(-limx_neg, txz)), cyz = fminf(limy_pos, fmaxf(-limy_neg, tyz));
-      const float ctx = cxz * tz, cty = cyz * tz;
-      const float j00 = fx * rz, j02 = -(fx * ctx) * rz * rz, j11 = fy * rz, j12 = -(fy * cty) * rz * rz;
-      const float t0[3] = {j00 * W[0] + j02 * W[8], j00 * W[1] + j02 * W[9], j00 * W[2] + j02 * W[10]};
-      const float t1[3] = {j11 * W[4] + j12 * W[8], j11 * W[5] + j12 * W[9], j11 * W[6] + j12 * W[10]};
-      const float a[3] = {t0[0] * S[0] + t0[1] * S[1] + t0[2] * S[2], t0[0] * S[1] + t0[1] * S[3] + t0[2] * S[4], t0[0] * S[2] + t0[1] * S[4] + t0[2] * S[5]};
-      const float b[3] = {t1[0] * S[0] + t1[1] * S[1] + t1[2] * S[2], t1[0] * S[1] + t1[1] * S[3] + t1[2] * S[4], t1[0] * S[2] + t1[1] * S[4] + t1[2] * S[5]};
-      const float c00 = a[0] * t0[0] + a[1] * t0[1] + a[2] * t0[2] + c.eps2d;
-      const float c01 = a[0] * t1[0] + a[1] * t1[1] + a[2] * t1[2];
-      const float c11 = b[0] * t1[0] + b[1] * t1[1] + b[2] * t1[2] + c.eps2d;
-      const float det = c00 * c11 - c01 * c01, rdet = 1.0f / det;
-      const float ca = c11 * rdet, cb = -c01 * rdet, cc = c00 * rdet;
-      // conic inverse
-      const float dLddet = -(gr[GR_CA] * ca + gr[GR_CB] * cb + gr[GR_CC] * cc) * rdet;
-      const float d00 = gr[GR_CC] * rdet + dLddet * c11, d11 = gr[GR_CA] * rdet + dLddet * c00, d01 = -gr[GR_CB] * rdet - 2.0f * dLddet * c01;
-      // 2-D covariance = M Sigma M^T (+ eps2d), M = J W (rows t0, t1)
-      float dt0[3], dt1[3];
-#pragma unroll
-      for (int i = 0; i < 3; ++i) {
-        dt0[i] = 2.0f * d00 * a[i] + d01 * b[i];
-        dt1[i] = 2.0f * d11 * b[i] + d01 * a[i];
-      }
-      gS[0] += d00 * t0[0] * t0[0] + d01 * t0[0] * t1[0] + d11 * t1[0] * t1[0];
-      gS[3] += d00 * t0[1] * t0[1] + d01 * t0[1] * t1[1] + d11 * t1[1] * t1[1];
-      gS[5] += d00 * t0[2] * t0[2] + d01 * t0[2] * t1[2] + d11 * t1[2] * t1[2];
-      gS[1] += 2.0f * d00 * t0[0] * t0[1] + d01 * (t0[0] * t1[1] + t0[1] * t1[0]) + 2.0f * d11 * t1[0] * t1[1];
-      gS[2] += 2.0f * d00 * t0[0] * t0[2] + d01 * (t0[0] * t1[2] + t0[2] * t1[0]) + 2.0f * d11 * t1[0] * t1[2];
-      gS[4] += 2.0f * d00 * t0[1] * t0[2] + d01 * (t0[1] * t1[2] + t0[2] * t1[1]) + 2.0f * d11 * t1[1] * t1[2];
+      const Lens lens = lens_k3(c);
+      const float fx = lens.fx, fy = lens.fy;
+      const Cov2D p = project_cov2d(lens, W, tx, ty, tz, S);
+      const Cov2DGrad q = project_cov2d_bwd(p, W, gr[GR_CA], gr[GR_CB], gr[GR_CC], gS);
       const float W0[3] = {W[0], W[1], W[2]}, W1[3] = {W[4], W[5], W[6]}, W2[3] = {W[8], W[9], W[10]};
-      const float dj00 = dt0[0] * W0[0] + dt0[1] * W0[1] + dt0[2] * W0[2], dj02 = dt0[0] * W2[0] + dt0[1] * W2[1] + dt0[2] * W2[2];
-      const float dj11 = dt1[0] * W1[0] + dt1[1] * W1[1] + dt1[2] * W1[2], dj12 = dt1[0] * W2[0] + dt1[1] * W2[1] + dt1[2] * W2[2];
       // Jacobian -> camera-space point (the clamp of txz / tyz passes nothing to the clamped component); mean2d = (fx txz + cx, fy tyz + cy)
-      float drz = dj00 * fx + dj11 * fy - 2.0f * fx * ctx * rz * dj02 - 2.0f * fy * cty * rz * dj12;
-      const float dctx = -fx * rz * rz * dj02, dcty = -fy * rz * rz * dj12;
-      float dtz = dctx * cxz + dcty * cyz;
-      const float dtxz = ((cxz == txz) ? dctx * tz : 0.f) + fx * gr[GR_MX], dtyz = ((cyz == tyz) ? dcty * tz : 0.f) + fy * gr[GR_MY];
+      const float rz = p.rz;
+      float drz = q.dj00 * fx + q.dj11 * fy - 2.0f * fx * p.ctx * rz * q.dj02 - 2.0f * fy * p.cty * rz * q.dj12;
+      const float dctx = -fx * rz * rz * q.dj02, dcty = -fy * rz * rz * q.dj12;
+      float dtz = dctx * p.cxz + dcty * p.cyz;
+      const float dtxz = ((p.cxz == p.txz) ? dctx * tz : 0.f) + fx * gr[GR_MX], dtyz = ((p.cyz == p.tyz) ? dcty * tz : 0.f) + fy * gr[GR_MY];
       const float dtx = dtxz * rz, dty = dtyz * rz;
       drz += dtxz * tx + dtyz * ty;
       dtz += -drz * rz * rz;
@@ -311,28 +272,18 @@ __global__ __launch_bounds__(256) void project_bwd_k3_kernel(const Cam* __restri
         // d loss / d R = (through the covariance: rows of M = J R) + dp m^T;  d loss / d t = dp
 #pragma unroll
         for (int i = 0; i < 3; ++i) {
-          dW[i] = j00 * dt0[i] + dp[0] * m[i];
-          dW[4 + i] = j11 * dt1[i] + dp[1] * m[i];
-          dW[8 + i] = j02 * dt0[i] + j12 * dt1[i] + dp[2] * m[i];
+          dW[i] = p.j00 * q.dt0[i] + dp[0] * m[i];
+          dW[4 + i] = p.j11 * q.dt1[i] + dp[1] * m[i];
+          dW[8 + i] = p.j02 * q.dt0[i] + p.j12 * q.dt1[i] + dp[2] * m[i];
         }
         dW[3] = dp[0], dW[7] = dp[1], dW[11] = dp[2];
       }
     }
-    if (pose_part) {  // (uniform: every thread of the workgroup runs every view)
-#pragma unroll
-      for (int k = 0; k < 12; ++k) {
-        const float s = wave_sum(dW[k]);
-        if (lane == 0) s_pose[wave][k] = s;
-      }
-      __syncthreads();
-      if (threadIdx.x < 12) {
-        const int k = threadIdx.x;
-        pose_part[((int64_t)blockIdx.x * V + v) * 12 + k] = s_pose[0][k] + s_pose[1][k] + s_pose[2][k] + s_pose[3][k];
-      }
-      __syncthreads();
-    }
+    // (uniform: every thread of the workgroup runs every view)
+    if (pose_part) block_sum_row<12>(dW, pose_part + ((int64_t)blockIdx.x * V + v) * 12);
   }
   if (!live) return;
+  // (kept in the kernel, in this form: as a shared function the [3,3] branch compiles to narrower stores and measured 1.3 % slower)
   g_means[3 * g] = gm[0];
   g_means[3 * g + 1] = gm[1];
   g_means[3 * g + 2] = gm[2];
@@ -348,28 +299,6 @@ __global__ __launch_bounds__(256) void project_bwd_k3_kernel(const Cam* __restri
     g_colors[3 * g] = gcol[0];
     g_colors[3 * g + 1] = gcol[1];
     g_colors[3 * g + 2] = gcol[2];
-  }
-}
-
-// pose_part [nblk, V, 12] -> g_viewmats [V, 4, 4] (rows 0..2 = d loss / d [R | t], row 3 = 0): one workgroup per view
-__global__ __launch_bounds__(256) void viewmat_reduce_kernel(int V, int64_t nblk, const float* __restrict__ pose_part, float* __restrict__ g_viewmats) {
-  __shared__ float s[4][12];
-  const int v = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  float acc[12];
-#pragma unroll
-  for (int k = 0; k < 12; ++k) acc[k] = 0.f;
-  for (int64_t b = threadIdx.x; b < nblk; b += 256)
-#pragma unroll
-    for (int k = 0; k < 12; ++k) acc[k] += pose_part[(b * V + v) * 12 + k];
-#pragma unroll
-  for (int k = 0; k < 12; ++k) {
-    const float t = wave_sum(acc[k]);
-    if (lane == 0) s[wave][k] = t;
-  }
-  __syncthreads();
-  if (threadIdx.x < 16) {
-    const int k = threadIdx.x;
-    g_viewmats[v * 16 + k] = k < 12 ? s[0][k] + s[1][k] + s[2][k] + s[3][k] : 0.f;
   }
 }
 
@@ -439,41 +368,17 @@ __global__ __launch_bounds__(256) void sh_eval_bwd_kernel(int64_t G, int ncoef, 
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   float gmv[3] = {0.f, 0.f, 0.f};
   if (g < G) {
-    const float dx_ = means[3 * g] - campos[0], dy_ = means[3 * g + 1] - campos[1], dz_ = means[3 * g + 2] - campos[2];
-    const float inv = 1.0f / sqrtf(dx_ * dx_ + dy_ * dy_ + dz_ * dz_);
-    const float x = dx_ * inv, y = dy_ * inv, z = dz_ * inv;
     const float* shp = sh + (size_t)g * ncoef * 3;
     float* gsp = g_sh + (size_t)g * ncoef * 3;
-    float rsum[3] = {0.5f, 0.5f, 0.5f};
-    sh_basis(x, y, z, degree, true, [&](int k, Dual bk) {
-#pragma unroll
-      for (int ch = 0; ch < 3; ++ch) rsum[ch] += bk.v * shp[3 * k + ch];
-    });
-    float gl[3];
-#pragma unroll
-    for (int ch = 0; ch < 3; ++ch) gl[ch] = rsum[ch] < 0.0f ? 0.0f : g_rgb[3 * g + ch];
     for (int k = (degree + 1) * (degree + 1); k < ncoef; ++k)
 #pragma unroll
       for (int ch = 0; ch < 3; ++ch) gsp[3 * k + ch] = 0.f;
-    float gd[3] = {0.f, 0.f, 0.f};
-    sh_basis(x, y, z, degree, true, [&](int k, Dual bk) {
-      float s = 0.f;
-#pragma unroll
-      for (int ch = 0; ch < 3; ++ch) {
-        gsp[3 * k + ch] = bk.v * gl[ch];
-        s += gl[ch] * shp[3 * k + ch];
-      }
-      gd[0] += s * bk.x;
-      gd[1] += s * bk.y;
-      gd[2] += s * bk.z;
-    });
-    const float dd = gd[0] * x + gd[1] * y + gd[2] * z;
-    gmv[0] = (gd[0] - x * dd) * inv;
-    gmv[1] = (gd[1] - y * dd) * inv;
-    gmv[2] = (gd[2] - z * dd) * inv;
-    g_means[3 * g] = gmv[0];
-    g_means[3 * g + 1] = gmv[1];
-    g_means[3 * g + 2] = gmv[2];
+    const float gcol[3] = {g_rgb[3 * g], g_rgb[3 * g + 1], g_rgb[3 * g + 2]};
+    const float3 gdm = sh_color_bwd(view_dir(means + 3 * g, campos), degree, true, gcol, [&](int k, int ch) { return shp[3 * k + ch]; },
+                                    [&](int k, int ch, float gv) { gsp[3 * k + ch] = gv; });
+    g_means[3 * g] = gmv[0] = gdm.x;
+    g_means[3 * g + 1] = gmv[1] = gdm.y;
+    g_means[3 * g + 2] = gmv[2] = gdm.z;
   }
   // the camera centre moves the direction the other way
 #pragma unroll
@@ -489,19 +394,11 @@ __global__ __launch_bounds__(256) void sh_eval_bwd_kernel(int64_t G, int ncoef, 
   }
 }
 
-int check_k3_views(const Cam* cams, int V, const char* who) {
-  SIU3R_CHECK(cams && V >= 1 && V <= 65535, "%s: bad view array (V = %d)", who, V);
-  for (int v = 0; v < V; ++v)
-    SIU3R_CHECK(cams[v].mode == 1 && cams[v].width == cams[0].width && cams[v].height == cams[0].height && cams[v].width > 0 && cams[v].height > 0,
-                "%s: the backward covers the gsplat family (mode 1) with one frame size per call", who);
-  return 0;
-}
-
 }  // namespace
 
 extern "C" int siu3r_raster_quad_lists(const siu3r_raster_cam* cams_host, int V, const void* cams_dev, int64_t G, const int32_t* tile_start,
                                        const int32_t* ids, int64_t cap_d, const float* rec, void* ws, int64_t ws_bytes, void* stream) {
-  if (int rc = check_k3_views(cams_host, V, "raster_quad_lists")) return rc;
+  if (int rc = check_views(cams_host, V, 1, "raster_quad_lists")) return rc;
   const Geo geo = make_geo(cams_host[0].width, cams_host[0].height);
   SIU3R_CHECK(cams_dev && tile_start && (ids || cap_d == 0 || G == 0) && (rec || G == 0) && ws && (((uintptr_t)ws) & 3) == 0, "raster_quad_lists: bad arguments");
   SIU3R_CHECK(cap_d > 0 && cap_d < (1ll << 31) && ws_bytes >= (int64_t)V * (16 * cap_d + 16 * (int64_t)geo.T), "raster_quad_lists: workspace too small");
@@ -516,7 +413,7 @@ extern "C" int siu3r_raster_composite_feat_bwd(const siu3r_raster_cam* cams_host
                                                const void* ws, int64_t cap_d, const float* rec, const float* feats, int channels, const float* out,
                                                const float* out_alpha, const float* g_out, const float* g_alpha, float* grad, float* g_feats,
                                                void* stream) {
-  if (int rc = check_k3_views(cams_host, V, "raster_composite_feat_bwd")) return rc;
+  if (int rc = check_views(cams_host, V, 1, "raster_composite_feat_bwd")) return rc;
   SIU3R_CHECK(cams_dev && tile_start && ws && out && out_alpha && g_out && g_alpha && (G == 0 || (rec && feats && grad && g_feats)),
               "raster_composite_feat_bwd: null pointer");
   SIU3R_CHECK(G >= 0 && G < (1ll << 31) && channels >= 1 && cap_d > 0 && cap_d < (1ll << 31) && (int64_t)G * channels < (1ll << 40),
@@ -540,7 +437,7 @@ extern "C" int siu3r_raster_composite_feat_bwd(const siu3r_raster_cam* cams_host
 extern "C" int siu3r_raster_project_bwd_k3(const siu3r_raster_cam* cams_host, int V, const void* cams_dev, int64_t G, const float* means, const float* cov,
                                            int cov_stride, const int32_t* rect, const float* grad, float* g_means, float* g_cov, float* g_opacities,
                                            float* g_colors, float* pose_part, void* stream) {
-  if (int rc = check_k3_views(cams_host, V, "raster_project_bwd_k3")) return rc;
+  if (int rc = check_views(cams_host, V, 1, "raster_project_bwd_k3")) return rc;
   SIU3R_CHECK(G >= 0 && G < (1ll << 31), "raster_project_bwd_k3: G = %ld out of range", (long)G);
   SIU3R_CHECK(cams_dev && (G == 0 || (means && cov && rect && grad && g_means && g_cov && g_opacities)), "raster_project_bwd_k3: null pointer");
   SIU3R_CHECK(cov_stride == 6 || cov_stride == 9, "raster_project_bwd_k3: cov_stride must be 6 or 9");
@@ -553,7 +450,7 @@ extern "C" int siu3r_raster_project_bwd_k3(const siu3r_raster_cam* cams_host, in
 
 extern "C" int siu3r_raster_viewmat_reduce(int V, int64_t nrows, const float* pose_part, float* g_viewmats, void* stream) {
   SIU3R_CHECK(V >= 1 && V <= 65535 && nrows >= 0 && g_viewmats && (nrows == 0 || pose_part), "raster_viewmat_reduce: bad arguments");
-  hipLaunchKernelGGL(viewmat_reduce_kernel, dim3(V), dim3(256), 0, (hipStream_t)stream, V, nrows, pose_part, g_viewmats);
+  hipLaunchKernelGGL((rows_reduce_kernel<12, 16>), dim3(V), dim3(256), 0, (hipStream_t)stream, V, nrows, pose_part, g_viewmats);
   SIU3R_LAUNCH_CHECK("siu3r_raster_viewmat_reduce");
   return 0;
 }

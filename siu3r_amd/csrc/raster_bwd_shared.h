@@ -1,7 +1,11 @@
 // What the two rasterizer backward units (raster_bwd.hip: the 3DGS family, raster_bwd_k3.hip: the gsplat family) share: the layout of
-// the per-(view, Gaussian) screen-space gradient record, the wave sum and the SH basis with its direction gradient.
+// the per-(view, Gaussian) screen-space gradient record, the wave sum and the per-workgroup partial rows with their reduction, the
+// backward of the covariance projection (project_cov2d, raster_shared.h), the SH basis with its direction gradient and the SH colour
+// backward, and the host-side check of a call's views.
 #pragma once
 #include <hip/hip_runtime.h>
+
+#include "raster_shared.h"
 
 namespace {
 
@@ -12,6 +16,80 @@ __device__ __forceinline__ float wave_sum(float x) {
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) x += __shfl_xor(x, o);
   return x;
+}
+
+// Sum of N per-thread terms over the workgroup (256 threads) into row[0 .. N), fixed order: wave sums, then the four waves through
+// LDS; row[N .. OUT) = 0.  Every thread of the workgroup must call it (barriers); it may be called again at once.
+template <int N, int OUT = N>
+__device__ __forceinline__ void block_sum_row(const float* x, float* __restrict__ row) {
+  __shared__ float s[4][N];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int k = 0; k < N; ++k) {
+    const float t = wave_sum(x[k]);
+    if (lane == 0) s[wave][k] = t;
+  }
+  __syncthreads();
+  if (threadIdx.x < OUT) {
+    const int k = threadIdx.x;
+    row[k] = k < N ? s[0][k] + s[1][k] + s[2][k] + s[3][k] : 0.f;
+  }
+  __syncthreads();
+}
+
+// part [nblk, V, N] (the partial rows of the projection backwards) -> out [V, OUT]: one workgroup per view, entries past N are 0
+// (N = 6, OUT = 6: the se(3) pose gradient; N = 12, OUT = 16: d loss / d [R | t] as a 4 x 4 matrix with a zero fourth row)
+template <int N, int OUT>
+__global__ __launch_bounds__(256) void rows_reduce_kernel(int V, int64_t nblk, const float* __restrict__ part, float* __restrict__ out) {
+  const int v = blockIdx.x;
+  float acc[N];
+#pragma unroll
+  for (int k = 0; k < N; ++k) acc[k] = 0.f;
+  for (int64_t b = threadIdx.x; b < nblk; b += 256)
+#pragma unroll
+    for (int k = 0; k < N; ++k) acc[k] += part[(b * V + v) * N + k];
+  block_sum_row<N, OUT>(acc, out + v * OUT);
+}
+
+// ---- projection backward: what both camera modes share -------------------------------------------------------------------------------
+// d loss / d conic (gca, gcb, gcc) -> through the conic inverse and the 2-D covariance M Sigma M^T (p: the forward chain, project_cov2d)
+// to the rows of M (dt0, dt1), the Jacobian entries (dj..) and, added into gS[6], the Gaussian's covariance
+struct Cov2DGrad {
+  float dt0[3], dt1[3], dj00, dj02, dj11, dj12;
+};
+__device__ __forceinline__ Cov2DGrad project_cov2d_bwd(const Cov2D& p, const float* W, float gca, float gcb, float gcc, float* gS) {
+  const float* t0 = p.t0;
+  const float* t1 = p.t1;
+  const float rdet = 1.0f / p.det;
+  const float ca = p.c11 * rdet, cb = -p.c01 * rdet, cc = p.c00 * rdet;
+  // conic inverse
+  const float dLddet = -(gca * ca + gcb * cb + gcc * cc) * rdet;
+  const float d00 = gcc * rdet + dLddet * p.c11, d11 = gca * rdet + dLddet * p.c00, d01 = -gcb * rdet - 2.0f * dLddet * p.c01;
+  // 2-D covariance = M Sigma M^T (+ blur), M = J W (rows t0, t1)
+  Cov2DGrad q;
+#pragma unroll
+  for (int i = 0; i < 3; ++i) {
+    q.dt0[i] = 2.0f * d00 * p.a[i] + d01 * p.b[i];
+    q.dt1[i] = 2.0f * d11 * p.b[i] + d01 * p.a[i];
+  }
+  gS[0] += d00 * t0[0] * t0[0] + d01 * t0[0] * t1[0] + d11 * t1[0] * t1[0];
+  gS[3] += d00 * t0[1] * t0[1] + d01 * t0[1] * t1[1] + d11 * t1[1] * t1[1];
+  gS[5] += d00 * t0[2] * t0[2] + d01 * t0[2] * t1[2] + d11 * t1[2] * t1[2];
+  gS[1] += 2.0f * d00 * t0[0] * t0[1] + d01 * (t0[0] * t1[1] + t0[1] * t1[0]) + 2.0f * d11 * t1[0] * t1[1];
+  gS[2] += 2.0f * d00 * t0[0] * t0[2] + d01 * (t0[0] * t1[2] + t0[2] * t1[0]) + 2.0f * d11 * t1[0] * t1[2];
+  gS[4] += 2.0f * d00 * t0[1] * t0[2] + d01 * (t0[1] * t1[2] + t0[2] * t1[1]) + 2.0f * d11 * t1[1] * t1[2];
+  q.dj00 = q.dt0[0] * W[0] + q.dt0[1] * W[1] + q.dt0[2] * W[2], q.dj02 = q.dt0[0] * W[8] + q.dt0[1] * W[9] + q.dt0[2] * W[10];
+  q.dj11 = q.dt1[0] * W[4] + q.dt1[1] * W[5] + q.dt1[2] * W[6], q.dj12 = q.dt1[0] * W[8] + q.dt1[1] * W[9] + q.dt1[2] * W[10];
+  return q;
+}
+
+// every view of a call: camera mode `mode`, one frame size
+inline int check_views(const siu3r_raster_cam* cams, int V, int mode, const char* who) {
+  SIU3R_CHECK(cams && V >= 1 && V <= 65535, "%s: bad view array (V = %d)", who, V);
+  for (int v = 0; v < V; ++v)
+    SIU3R_CHECK(cams[v].mode == mode && cams[v].width == cams[0].width && cams[v].height == cams[0].height && cams[v].width > 0 && cams[v].height > 0,
+                "%s: the backward covers the %s family (mode %d) with one frame size per call", who, mode == 0 ? "3DGS" : "gsplat", mode);
+  return 0;
 }
 
 // ---- SH basis with its gradient w.r.t. the (unit) view direction ---------------------------------------------------------------------
@@ -66,6 +144,45 @@ __device__ __forceinline__ void sh_basis(float dx_, float dy_, float dz_, int de
   f(22, c_B4[6] * ((xx - yy) * (7.0f * zz - 1.0f)));
   f(23, c_B4[7] * (xz * (xx - 3.0f * yy)));
   f(24, c_B4[8] * (xx * (xx - 3.0f * yy) - yy * (3.0f * xx - yy)));
+}
+
+// unit view direction d = (m - campos) / |m - campos| with 1 / |m - campos|
+struct ViewDir {
+  float x, y, z, inv;
+};
+__device__ __forceinline__ ViewDir view_dir(const float* m, const float* campos) {
+  const float ddx = m[0] - campos[0], ddy = m[1] - campos[1], ddz = m[2] - campos[2];
+  const float len = sqrtf(ddx * ddx + ddy * ddy + ddz * ddz), inv = 1.0f / len;
+  return {ddx * inv, ddy * inv, ddz * inv, inv};
+}
+// Backward of rgb = max(sum_k B_k(d) coef(k, ch) + 0.5, 0) for the upstream colour gradient gcol[3]: a channel clamped at 0 passes
+// nothing; sink(k, ch, value) takes d loss / d coef(k, ch) for the coefficients the forward's polynomial uses.  Returns d loss / d m
+// through the direction: the gradient w.r.t. d, projected off d and divided by the length.
+template <class Coef, class Sink>
+__device__ __forceinline__ float3 sh_color_bwd(const ViewDir d, int deg, bool band4, const float* gcol, Coef&& coef, Sink&& sink) {
+  // which channels the +0.5 / clamp-at-0 left alive
+  float rsum[3] = {0.5f, 0.5f, 0.5f};
+  sh_basis(d.x, d.y, d.z, deg, band4, [&](int k, Dual bk) {
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) rsum[ch] += bk.v * coef(k, ch);
+  });
+  float gl[3];
+#pragma unroll
+  for (int ch = 0; ch < 3; ++ch) gl[ch] = rsum[ch] < 0.0f ? 0.0f : gcol[ch];
+  float gd[3] = {0.f, 0.f, 0.f};
+  sh_basis(d.x, d.y, d.z, deg, band4, [&](int k, Dual bk) {
+    float s = 0.f;
+#pragma unroll
+    for (int ch = 0; ch < 3; ++ch) {
+      sink(k, ch, bk.v * gl[ch]);
+      s += gl[ch] * coef(k, ch);
+    }
+    gd[0] += s * bk.x;
+    gd[1] += s * bk.y;
+    gd[2] += s * bk.z;
+  });
+  const float dd = gd[0] * d.x + gd[1] * d.y + gd[2] * d.z;
+  return make_float3((gd[0] - d.x * dd) * d.inv, (gd[1] - d.y * dd) * d.inv, (gd[2] - d.z * dd) * d.inv);
 }
 
 __device__ __forceinline__ void cross3(const float* a, const float* b, float* o) {

@@ -19,6 +19,7 @@ from ._lib import RasterCam, check
 from .ops import _gpu, _p, _stream
 
 TILE = 16
+GR_N = 10  # floats per (view, Gaussian) screen-space gradient record (csrc/raster_bwd_shared.h)
 
 
 def _set(arr, values):
@@ -343,7 +344,7 @@ class _RasterizeK2(torch.autograd.Function):
         o = _rasterize_views_k2(cams, means.detach(), cov6.detach(), shs.detach(), opacities.detach(), check_overflow=True, **kw)
         st = o["state"]
         ctx.st, ctx.sh_planar = st, kw["sh_planar"]
-        ctx.shapes = [(t.shape, t.dtype) if isinstance(t, torch.Tensor) else None for t in (means, cov6, shs, opacities, pose_delta, means2d)]
+        ctx.shapes = _shapes(means, cov6, shs, opacities, pose_delta, means2d)
         # private copies of the totals the backward needs: callers may modify the returned maps in place (image.clamp_(0, 1))
         ctx.save_for_backward(means, cov6, shs, opacities, o["image"].clone(), o["depth"].clone(), o["opacity"].clone())
         nd = [o["radii"]] + ([o["n_touched"]] if o["n_touched"] is not None else [])
@@ -357,11 +358,10 @@ class _RasterizeK2(torch.autograd.Function):
         st = ctx.st
         lib = _lib.lib()
         V, G, dev = st["V"], st["G"], image.device
-        z = lambda ref, g: torch.zeros_like(ref) if g is None else g.detach().float().contiguous()
-        g_image, g_depth, g_opacity = z(image, g_image), z(depth, g_depth), z(opacity, g_opacity)
+        g_image, g_depth, g_opacity = _upstream(image, g_image), _upstream(depth, g_depth), _upstream(opacity, g_opacity)
         means_c, cov_c, shs_c, op_c = (t.detach().contiguous().float() for t in (means, cov6, shs, opacities))
         ncoef = shs_c.shape[2] if ctx.sh_planar else shs_c.shape[1]
-        grad = torch.empty((V, G, 10), dtype=torch.float32, device=dev)
+        grad = torch.empty((V, G, GR_N), dtype=torch.float32, device=dev)
         check(lib.siu3r_raster_composite_rgb_bwd(st["cams"], V, _p(st["cams_dev"]), G, _p(st["bin_start"]), _p(st["entries"]), st["cap_e"], _p(st["rec"]),
                                                  _p(image), _p(depth), _p(opacity), _p(g_image), _p(g_depth), _p(g_opacity), _p(grad), _stream()))
         need_pose, need_m2d = ctx.needs_input_grad[6], ctx.needs_input_grad[7]
@@ -380,17 +380,10 @@ class _RasterizeK2(torch.autograd.Function):
             check(lib.siu3r_raster_pose_reduce(V, rows, _p(part), _p(g_pose), _stream()))
         g_mean2d = None
         if need_m2d:
-            shape, dtype = ctx.shapes[5]
+            shape, dtype, _ = ctx.shapes[5]
             g_mean2d = torch.zeros(shape, dtype=dtype, device=dev)
             g_mean2d[:, :2] = g_m2d.sum(0).to(dtype)
-        out = []
-        for i, g in enumerate((g_means, g_cov, g_sh, g_op, g_pose)):
-            if not ctx.needs_input_grad[2 + i]:
-                out.append(None)
-                continue
-            shape, dtype = ctx.shapes[i]
-            out.append(g.reshape(shape).to(dtype))
-        return (None, None, *out, g_mean2d)
+        return (None, None, *_grads_out(ctx, 2, (g_means, g_cov, g_sh, g_op, g_pose)), g_mean2d)
 
 
 def _rasterize_views_k2(cams: Sequence[RasterCam], means, cov6, shs, opacities, want_n_touched=True, entry_capacity=None,
@@ -427,6 +420,11 @@ def tune(key: int, value: int) -> None:
     check(_lib.lib().siu3r_raster_tune(int(key), int(value)))
 
 
+def _upstream(ref, g):
+    """an upstream gradient as the kernels read it (fp32, contiguous); zeros like the output where autograd hands over None"""
+    return torch.zeros_like(ref) if g is None else g.detach().float().contiguous()
+
+
 def _wants_grad(*ts) -> bool:
     return torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in ts)
 
@@ -456,6 +454,11 @@ def rasterize_views_k3(cams: Sequence[RasterCam], means, cov6, opacities, feats,
     return _rasterize_views_k3(cams, means, cov6, opacities, feats, entry_capacity, pair_capacity, check_overflow, pose_dev, matrix_form, pose_c2w)
 
 
+def _shapes(*ts):
+    """what _grads_out needs of forward's differentiable arguments"""
+    return [(t.shape, t.dtype, t.device) if isinstance(t, torch.Tensor) else None for t in ts]
+
+
 def _grads_out(ctx, first, grads):
     """the gradients of the differentiable inputs (index first.. of forward's arguments) in their shapes / dtypes / devices (a pose handed
     over on the host gets its gradient there), None where not needed"""
@@ -470,7 +473,7 @@ def _grads_out(ctx, first, grads):
 
 
 def _project_bwd_k3(st, means, cov6, grad, need_pose, g_colors=None):
-    """the mode-1 projection backward of a finished composite backward (grad [V,G,10]) -> g_means, g_cov, g_opacities, g_viewmats [V,4,4]"""
+    """the mode-1 projection backward of a finished composite backward (grad [V,G,GR_N]) -> g_means, g_cov, g_opacities, g_viewmats [V,4,4]"""
     lib = _lib.lib()
     V, G, dev = st["V"], st["G"], means.device
     g_means, g_cov, g_op = torch.empty_like(means), torch.empty_like(cov6), torch.empty((G,), dtype=torch.float32, device=dev)
@@ -485,6 +488,20 @@ def _project_bwd_k3(st, means, cov6, grad, need_pose, g_colors=None):
     return g_means, g_cov, g_op, g_vm
 
 
+def _k3_forward(ctx, render, save_chan, cams, kw, means, cov6, opacities, chan, viewmats):
+    """forward of both K3 autograd functions: chan = feats [G,C] (which the N-channel backward reads again: save_chan) or rgb [G,3]"""
+    kw = dict(kw)
+    Ks = kw.pop("Ks")
+    pose_dev = None if viewmats is None else (viewmats, Ks)
+    o = render(cams, means.detach(), cov6.detach(), opacities.detach(), chan.detach(), check_overflow=True, pose_dev=pose_dev, **kw)
+    ctx.st = o["state"]
+    ctx.shapes = _shapes(means, cov6, opacities, chan, viewmats)
+    # private copies of the totals the backward needs: callers may modify the returned maps in place
+    ctx.save_for_backward(means, cov6, *((chan,) if save_chan else ()), o["colors"].clone(), o["alphas"].clone())
+    ctx.mark_non_differentiable(o["radii"])
+    return o["colors"], o["alphas"], o["radii"], o["state"]
+
+
 class _RasterizeK3(torch.autograd.Function):
     """The K3 N-channel forward (unchanged kernels, synchronous overflow check) and its HIP backward (csrc/raster_bwd_k3.hip): composite
     backward over the per-quadrant lists (the forward's workspace, or built here) -> per-(view, Gaussian) screen-space gradients and the
@@ -492,16 +509,7 @@ class _RasterizeK3(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, cams, kw, means, cov6, opacities, feats, viewmats):
-        kw = dict(kw)
-        Ks = kw.pop("Ks")
-        pose_dev = None if viewmats is None else (viewmats, Ks)
-        o = _rasterize_views_k3(cams, means.detach(), cov6.detach(), opacities.detach(), feats.detach(), check_overflow=True, pose_dev=pose_dev, **kw)
-        ctx.st = o["state"]
-        ctx.shapes = [(t.shape, t.dtype, t.device) if isinstance(t, torch.Tensor) else None for t in (means, cov6, opacities, feats, viewmats)]
-        # private copies of the totals the backward needs: callers may modify the returned maps in place
-        ctx.save_for_backward(means, cov6, feats, o["colors"].clone(), o["alphas"].clone())
-        ctx.mark_non_differentiable(o["radii"])
-        return o["colors"], o["alphas"], o["radii"], o["state"]
+        return _k3_forward(ctx, _rasterize_views_k3, True, cams, kw, means, cov6, opacities, feats, viewmats)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
@@ -510,8 +518,7 @@ class _RasterizeK3(torch.autograd.Function):
         st = ctx.st
         lib = _lib.lib()
         V, G, dev = st["V"], st["G"], colors.device
-        z = lambda ref, g: torch.zeros_like(ref) if g is None else g.detach().float().contiguous()
-        g_colors, g_alphas = z(colors, g_colors), z(alphas, g_alphas)
+        g_colors, g_alphas = _upstream(colors, g_colors), _upstream(alphas, g_alphas)
         means_c, cov_c, feats_c = (t.detach().contiguous().float() for t in (means, cov6, feats))
         Cc = feats_c.shape[1]
         tstart, ids_all, cap_d = st["tile_start_all"], st["ids_all"], st["cap_d"]
@@ -523,7 +530,7 @@ class _RasterizeK3(torch.autograd.Function):
                 ws = torch.empty((int(lib.siu3r_raster_composite_feat_ws_bytes(st["W"], st["H"], V, cap_d)) // 4,), dtype=torch.int32, device=dev)
             check(lib.siu3r_raster_quad_lists(st["cams"], V, _p(st["cams_dev"]), G, _p(tstart), _p(ids_all), cap_d, _p(st["rec"]), _p(ws),
                                               ws.numel() * 4, _stream()))
-        grad = torch.empty((V, G, 10), dtype=torch.float32, device=dev)
+        grad = torch.empty((V, G, GR_N), dtype=torch.float32, device=dev)
         g_feats = torch.empty_like(feats_c)
         check(lib.siu3r_raster_composite_feat_bwd(st["cams"], V, _p(st["cams_dev"]), G, _p(tstart), _p(ws), cap_d, _p(st["rec"]), _p(feats_c), Cc,
                                                   _p(colors), _p(alphas), _p(g_colors), _p(g_alphas), _p(grad), _p(g_feats), _stream()))
@@ -582,15 +589,7 @@ class _RasterizeK3RGB(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, cams, kw, means, cov6, opacities, rgb, viewmats):
-        kw = dict(kw)
-        Ks = kw.pop("Ks")
-        pose_dev = None if viewmats is None else (viewmats, Ks)
-        o = _rasterize_views_k3_rgb(cams, means.detach(), cov6.detach(), opacities.detach(), rgb.detach(), check_overflow=True, pose_dev=pose_dev, **kw)
-        ctx.st = o["state"]
-        ctx.shapes = [(t.shape, t.dtype, t.device) if isinstance(t, torch.Tensor) else None for t in (means, cov6, opacities, rgb, viewmats)]
-        ctx.save_for_backward(means, cov6, o["colors"].clone(), o["alphas"].clone())
-        ctx.mark_non_differentiable(o["radii"])
-        return o["colors"], o["alphas"], o["radii"], o["state"]
+        return _k3_forward(ctx, _rasterize_views_k3_rgb, False, cams, kw, means, cov6, opacities, rgb, viewmats)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
@@ -599,10 +598,9 @@ class _RasterizeK3RGB(torch.autograd.Function):
         st = ctx.st
         lib = _lib.lib()
         V, G, dev = st["V"], st["G"], colors.device
-        z = lambda ref, g: torch.zeros_like(ref) if g is None else g.detach().float().contiguous()
-        g_colors, g_alphas = z(colors, g_colors), z(alphas, g_alphas)
+        g_colors, g_alphas = _upstream(colors, g_colors), _upstream(alphas, g_alphas)
         means_c, cov_c = means.detach().contiguous().float(), cov6.detach().contiguous().float()
-        grad = torch.empty((V, G, 10), dtype=torch.float32, device=dev)
+        grad = torch.empty((V, G, GR_N), dtype=torch.float32, device=dev)
         check(lib.siu3r_raster_composite_rgb_bwd_k3(st["cams"], V, _p(st["cams_dev"]), G, _p(st["bin_start"]), _p(st["entries"]), st["cap_e"],
                                                     _p(st["rec"]), _p(colors), _p(alphas), _p(g_colors), _p(g_alphas), _p(grad), _stream()))
         g_rgb = torch.empty((G, 3), dtype=torch.float32, device=dev)
