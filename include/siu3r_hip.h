@@ -489,6 +489,35 @@ int siu3r_photo_loss(const float* pred, const float* target, int V, int C, int H
                      const int64_t* target_strides, float lambda, float data_range, float* grad_pred, float* partials, float* out,
                      void* stream);
 
+/* ---- adaptive density control of splat refinement (csrc/density.hip; Kerbl et al. 2023, section 5.2): clone / split / prune ----
+ * Deterministic (no float atomics; two calls on the same input give the same bits), nothing allocates or synchronises with the host.
+ * Statistics, every iteration.  g_mean2d [V,G,2]: the pixel-space mean gradient as siu3r_raster_project_bwd writes it (rows of culled
+ * Gaussians are never read: visibility is radii > 0); radii [V,G,2] i32.  For every view, in index order, with radii[v,g,0] > 0 or
+ * radii[v,g,1] > 0:  grad_accum[g] += hypot(sx gx, sy gy), seen[g] += 1, max_radius[g] = max(max_radius[g], radii[v,g,:]).  The three
+ * running arrays ([G] f32 / i32 / i32) are read and written. */
+int siu3r_density_accumulate(const float* g_mean2d, const int32_t* radii, int V, int64_t G, float sx, float sy, float* grad_accum,
+                             int32_t* seen, int32_t* max_radius, void* stream);
+/* Plan.  action[g]: 0 prune (no output row), 1 keep (1), 2 clone (2), 3 split (2), from
+ *   avg = seen > 0 ? grad_accum / seen : 0 (an fp64 quotient),  hot = avg >= grad_threshold,  big = max_k log_scales[g,k] > log_dense_scale,
+ *   prune = logit_opacity[g] < logit_min_opacity  ||  (max_screen_radius > 0 && max_radius[g] > max_screen_radius)
+ *           ||  max_k log_scales[g,k] > log_max_world_scale  (+infinity switches it off);
+ *   prune -> 0, else hot && grow -> (big ? 3 : 2), else 1.
+ * offset [G]: the exclusive scan of the output rows in memory order (rows of g: offset[g] .. offset[g] + rows - 1); totals [4] = rows out,
+ * pruned, cloned, split; ws: siu3r_density_plan_ws(G) int32 of workspace.  All of these live on the device.  G <= 2^30. */
+int64_t siu3r_density_plan_ws(int64_t G);
+int siu3r_density_plan(const float* grad_accum, const int32_t* seen, const int32_t* max_radius, const float* log_scales,
+                       const float* logit_opacity, int64_t G, float grad_threshold, float log_dense_scale, float logit_min_opacity,
+                       int max_screen_radius, float log_max_world_scale, int grow, int32_t* action, int32_t* offset, int32_t* ws,
+                       int32_t* totals, void* stream);
+/* Apply, one call per field: gathers src [G,r] fp32 (and its Adam moments m1 / m2 [G,r], both or neither) into dst / dst_m1 / dst_m2
+ * [rows out, r].  keep: the row's bits and moments; clone: the bits twice, the second row with zero moments; split: two rows with zero
+ * moments, by mode:  0 the parent's bits;  1 (means, r = 3) mean + R(q / |q|) (exp(log_scales[g]) o noise[g,c,:]) for child c, with
+ * quats_xyzw [G,4] raw (x, y, z, w), log_scales [G,3] and noise [G,2,3] (the caller's unit normals);  2 (log-scales, r = 3) - log(1.6).
+ * The three extra inputs are read in mode 1 only.  G * r < 2^31. */
+int siu3r_density_apply(int mode, const float* src, const float* m1, const float* m2, int r, int64_t G, const int32_t* action,
+                        const int32_t* offset, const float* quats_xyzw, const float* log_scales, const float* noise, float* dst,
+                        float* dst_m1, float* dst_m2, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

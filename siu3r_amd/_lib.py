@@ -147,12 +147,17 @@ SIGNATURES = {
     "siu3r_sh_eval_bwd": [_P, _P, _P, _I, _I, _P, _P, _P, _P, _L, _P],
     "siu3r_photo_loss_partials": [_I, _I, _I, _I],
     "siu3r_photo_loss": [_P, _P, _I, _I, _I, _I, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _F, _F, _P, _P, _P, _P],
+    "siu3r_density_accumulate": [_P, _P, _I, _L, _F, _F, _P, _P, _P, _P],
+    "siu3r_density_plan_ws": [_L],
+    "siu3r_density_plan": [_P, _P, _P, _P, _P, _L, _F, _F, _F, _I, _F, _I, _P, _P, _P, _P, _P],
+    "siu3r_density_apply": [_I, _P, _P, _P, _I, _L, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "siu3r_lift_ids": [_P, _I, _I, _I, _I, _I, _F, _I, C.c_uint32, _P, _P, _P, _P, _P],
     "siu3r_panoptic_stage1": [_P] * 20 + [_I] * 9 + [_F, _F, _F, C.c_uint32, _P],
     "siu3r_panoptic_qcl": [_P, _P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P],
 }
 _RESTYPES = {"siu3r_last_error": C.c_char_p, "siu3r_raster_composite_feat_ws_bytes": C.c_int64, "siu3r_raster_pose_partial_rows": C.c_int64}
 _RESTYPES["siu3r_photo_loss_partials"] = C.c_int64
+_RESTYPES["siu3r_density_plan_ws"] = C.c_int64
 
 _lib = None
 

@@ -45,7 +45,8 @@ def get_projection_matrix(near, far, fov_x, fov_y) -> torch.Tensor:
 
 def render_cuda(extrinsics, intrinsics, near, far, image_shape, background_color, gaussian_means, gaussian_covariances,
                 gaussian_sh_coefficients, gaussian_opacities, use_sh: bool = True, cam_rot_delta=None, cam_trans_delta=None,
-                sh_band4: bool = False, return_aux: bool = False, entry_capacity=None, check_overflow=True, translation_scale: float = 1.0):
+                sh_band4: bool = False, return_aux: bool = False, entry_capacity=None, check_overflow=True, translation_scale: float = 1.0,
+                density_stats=None):
     """reference signature cuda_splatting.py:46-60 (batch = views).  Returns (images [b,3,h,w], depths [b,h,w]); return_aux adds the
     per-call outputs (radii, n_touched, opacity, binning state).  entry_capacity: optional size of the coarse-bin entry buffers (an
     overflow of the default bound is detected and the call repeated with the exact size).  check_overflow: True (synchronous, as the
@@ -57,7 +58,10 @@ def render_cuda(extrinsics, intrinsics, near, far, image_shape, background_color
     entries the forward reads), SH coefficients and opacities (HIP backward, csrc/raster_bwd.hip).  cam_rot_delta / cam_trans_delta
     ([b,3] each, theta / rho): per-view gradient holders of a LEFT perturbation of the world->camera pose the render uses (translation
     already scaled by translation_scale), w2c <- exp(xi^) w2c, xi = (trans, rot), taken at xi = 0; the render uses the extrinsics as given.
-    Views whose Gaussians are expanded from one tensor still render as one multi-view call; autograd sums their gradients."""
+    Views whose Gaussians are expanded from one tensor still render as one multi-view call; autograd sums their gradients.
+    density_stats: a density.DensityStats that the backward fills with the densification statistics of this render (per-view position
+    gradient norms, visibility counts, largest radii: raster.rasterize_views_k2); the views must then share ONE Gaussian set.  None, the
+    default, changes nothing."""
     assert use_sh or gaussian_sh_coefficients.shape[-1] == 1
     if (cam_rot_delta is None) != (cam_trans_delta is None):
         raise ValueError("pass cam_rot_delta and cam_trans_delta together (one se(3) update per view)")
@@ -91,6 +95,8 @@ def render_cuda(extrinsics, intrinsics, near, far, image_shape, background_color
             j += 1
         groups.append((i, j))
         i = j
+    if density_stats is not None and len(groups) != 1:
+        raise ValueError("density_stats counts per Gaussian of ONE set: expand the views from the same tensors")
     images, depths, aux = [], [], []
     bg_h = background_color.detach().float().cpu()
     for (i0, i1) in groups:
@@ -109,7 +115,7 @@ def render_cuda(extrinsics, intrinsics, near, far, image_shape, background_color
         delta = None if cam_rot_delta is None else torch.cat((cam_trans_delta[i0:i1], cam_rot_delta[i0:i1]), dim=-1).float()
         out = raster.rasterize_views_k2(cams, gaussian_means[i0], gaussian_covariances[i0], sh_i if planar else sh_i.permute(0, 2, 1).contiguous(),
                                         gaussian_opacities[i0], want_n_touched=return_aux, entry_capacity=entry_capacity, sh_planar=planar,
-                                        check_overflow=check_overflow, pose_c2w=pose, pose_delta=delta)
+                                        check_overflow=check_overflow, pose_c2w=pose, pose_delta=delta, **({} if density_stats is None else {"density_stats": density_stats}))
         images.append(out["image"])
         depths.append(out["depth"])
         aux.append(out)

@@ -313,7 +313,8 @@ def _with_retry(run, entry_capacity, check_overflow):
 
 
 def rasterize_views_k2(cams: Sequence[RasterCam], means, cov6, shs, opacities, want_n_touched=True, entry_capacity=None,
-                       check_overflow=True, sh_planar=False, pose_c2w=None, pose_delta=None, means2d=None) -> Dict[str, torch.Tensor]:
+                       check_overflow=True, sh_planar=False, pose_c2w=None, pose_delta=None, means2d=None, density_stats=None
+                       ) -> Dict[str, torch.Tensor]:
     """V views of one Gaussian set.  means [G,3]; cov6 [G,6] (upper triangle) or [G,3,3]; shs [G,ncoef,3], or with sh_planar
     [G,3,25] (Gaussians.harmonics as stored); opacities [G] (fp32, GPU) -> image [V,3,H,W], radii [V,G,2] i32, depth [V,H,W],
     opacity [V,H,W], n_touched [V,G] i32 (None when not wanted) + the call's state.
@@ -321,7 +322,10 @@ def rasterize_views_k2(cams: Sequence[RasterCam], means, cov6, shs, opacities, w
     Differentiable when grad mode is on and means / cov6 / shs / opacities / pose_delta / means2d requires grad (_RasterizeK2; the
     outputs are the same bits as without grad).  pose_delta [V,6] = (rho, theta): a left se(3) perturbation w2c <- exp(xi^) w2c of each
     view, a gradient holder taken at xi = 0 (the render uses the poses as given).  means2d [G,k>=2]: a gradient holder that receives the
-    pixel-space mean gradient summed over the views (the caller scales it).  Every other call runs the plain forward."""
+    pixel-space mean gradient summed over the views (the caller scales it).  Every other call runs the plain forward.
+    density_stats: a density.DensityStats of G Gaussians; the backward of a differentiable call accumulates the per-view NDC-space mean
+    gradient norms (scaled by V: DensityStats.accumulate), the visibility counts and the largest radii into it.  The forward does not
+    look at it, and None (the default) leaves the backward exactly as it is without the keyword."""
     diff = (means, cov6, shs, opacities, pose_delta, means2d)
     if torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in diff):
         if check_overflow == "deferred":
@@ -330,6 +334,10 @@ def rasterize_views_k2(cams: Sequence[RasterCam], means, cov6, shs, opacities, w
         if pose_delta is not None and tuple(pose_delta.shape) != (len(cams), 6):
             raise ValueError(f"pose_delta must be [V, 6] = (rho, theta) per view, got {tuple(pose_delta.shape)}")
         kw = dict(want_n_touched=want_n_touched, entry_capacity=entry_capacity, sh_planar=sh_planar, pose_c2w=pose_c2w)
+        if density_stats is not None:
+            if density_stats.G != means.shape[0]:
+                raise ValueError(f"density_stats holds {density_stats.G} Gaussians, the render has {means.shape[0]}")
+            kw["density_stats"] = density_stats
         image, depth, opacity, radii, n_touched, st = _RasterizeK2.apply(list(cams), kw, means, cov6, shs, opacities, pose_delta, means2d)
         return dict(image=image, radii=radii, depth=depth, opacity=opacity, n_touched=n_touched, state=st)
     return _rasterize_views_k2(cams, means, cov6, shs, opacities, want_n_touched, entry_capacity, check_overflow, sh_planar, pose_c2w)
@@ -341,6 +349,8 @@ class _RasterizeK2(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, cams, kw, means, cov6, shs, opacities, pose_delta, means2d):
+        kw = dict(kw)
+        ctx.density_stats = kw.pop("density_stats", None)
         o = _rasterize_views_k2(cams, means.detach(), cov6.detach(), shs.detach(), opacities.detach(), check_overflow=True, **kw)
         st = o["state"]
         ctx.st, ctx.sh_planar = st, kw["sh_planar"]
@@ -365,13 +375,18 @@ class _RasterizeK2(torch.autograd.Function):
         check(lib.siu3r_raster_composite_rgb_bwd(st["cams"], V, _p(st["cams_dev"]), G, _p(st["bin_start"]), _p(st["entries"]), st["cap_e"], _p(st["rec"]),
                                                  _p(image), _p(depth), _p(opacity), _p(g_image), _p(g_depth), _p(g_opacity), _p(grad), _stream()))
         need_pose, need_m2d = ctx.needs_input_grad[6], ctx.needs_input_grad[7]
+        stats = ctx.density_stats
         g_means, g_cov, g_op, g_sh = torch.empty_like(means_c), torch.empty_like(cov_c), torch.empty_like(op_c), torch.empty_like(shs_c)
         g_m2d = torch.zeros((V, G, 2), dtype=torch.float32, device=dev) if need_m2d else None  # (culled Gaussians: not written)
+        if stats is not None and g_m2d is None:
+            g_m2d = torch.empty((V, G, 2), dtype=torch.float32, device=dev)  # (the statistics go by the radii, never by an unwritten row)
         rows = int(lib.siu3r_raster_pose_partial_rows(G))
         part = torch.empty((max(rows, 1), V, 6), dtype=torch.float32, device=dev) if need_pose else None
         check(lib.siu3r_raster_project_bwd(st["cams"], V, _p(st["cams_dev"]), G, _p(means_c), _p(cov_c), _cov_stride(cov_c), _p(op_c), _p(shs_c), ncoef,
                                            int(bool(ctx.sh_planar)), _p(st["rect"]), _p(grad), _p(g_means), _p(g_cov), _p(g_op), _p(g_sh), _p(g_m2d),
                                            _p(part), _stream()))
+        if stats is not None:
+            stats.accumulate(g_m2d, st["radii"], 0.5 * V * st["W"], 0.5 * V * st["H"])
         g_pose = None
         if need_pose:
             g_pose = torch.empty((V, 6), dtype=torch.float32, device=dev)

@@ -4,12 +4,14 @@ loss (losses.photometric_loss) and one backward; the optimiser is torch's Adam. 
 (align_pose) and refines second."""
 from __future__ import annotations
 
+import math
 from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
 
 from . import raster
 from .cuda_splatting import render_cuda
+from .density import DensityControl, DensityStats, densify_and_prune, scene_extent
 from .losses import photometric_loss
 
 FIELDS = ("means", "scales", "rotations", "opacities", "harmonics")
@@ -26,8 +28,8 @@ def covariances_from(rotations_xyzw: torch.Tensor, scales: torch.Tensor) -> torc
 
 
 def refine_gaussians(means, scales, rotations, opacities, harmonics, images, c2w, Kn, near, far, bg, iters: int = 200, lambda_dssim: float = 0.2,
-                     lrs: Optional[Dict[str, float]] = None, params: Sequence[str] = FIELDS, log_every: int = 1
-                     ) -> Tuple[Dict[str, torch.Tensor], List[float]]:
+                     lrs: Optional[Dict[str, float]] = None, params: Sequence[str] = FIELDS, log_every: int = 1,
+                     density: Optional[DensityControl] = None) -> Tuple[Dict[str, torch.Tensor], List[float]]:
     """means [G,3], scales [G,3], rotations [G,4], opacities [G], harmonics [G,3,n] (n = (deg+1)^2): what `Gaussians` carries, on the GPU.
     images [V,3,H,W]: the posed target views; c2w [V,4,4] camera-to-world, Kn [V,3,3] (or [3,3]) normalised intrinsics, near / far floats
     (or [V]), bg 3 floats: render_cuda's conventions.
@@ -42,7 +44,20 @@ def refine_gaussians(means, scales, rotations, opacities, harmonics, images, c2w
     group per field; `lrs` overrides DEFAULT_LRS per field.  iters = 0 moves nothing.
 
     Returns ({"means", "scales", "rotations", "opacities", "harmonics", "covariances" [G,3,3]}: new tensors, the inputs are not modified;
-    the losses of the logged iterations: every `log_every`-th, each costing one host read; log_every = 0 reads nothing)."""
+    the losses of the logged iterations: every `log_every`-th, each costing one host read; log_every = 0 reads nothing).
+
+    density: a density.DensityControl turns on adaptive density control (3DGS section 5.2); None, the default, is the path above and
+    returns the same bits as a call without the keyword.  With a control every backward also accumulates the densification statistics
+    (density.DensityStats), and at the iterations control.events(iters) names, before that iteration's render, ALL five fields in their
+    unconstrained form and the Adam moments of the free ones go through density.densify_and_prune: Gaussians are cloned, split and
+    pruned in memory order, survivors keep their exp_avg / exp_avg_sq, new rows start from zero moments, the optimiser is rebuilt on the
+    new leaves with each group's step count preserved, and the statistics start over.  One host read per event (the new row count).
+    `params` only governs what Adam moves: a control together with frozen geometry still clones and prunes, and the children of a split
+    still get their own means and the smaller scale.  Frozen means, rotations and harmonics keep the bits of the rows that survive;
+    frozen scales / opacities make one round trip through log / logit at the first event.  An opacity reset clamps the free logit
+    opacities to at most logit(control.reset_opacity) and zeroes their moments (frozen opacities could never recover and are left
+    alone).  Every returned tensor then has the new row count, and the dict gains "density_events": one info dict per event
+    (densify_and_prune's counts plus "iteration").  control.scene_extent = None costs one host read of the camera centres."""
     params = tuple(params)
     for p in params:
         if p not in FIELDS:
@@ -77,13 +92,52 @@ def refine_gaussians(means, scales, rotations, opacities, harmonics, images, c2w
     cov6_fixed = None if cov_moves else cov6_of()
 
     losses: List[float] = []
+    events: List[dict] = []
+    new_adam = lambda: torch.optim.Adam([{"params": [free[k]], "lr": lr[k]} for k in free], eps=1e-15, fused=True)
+    stats, densify_at, reset_at = None, (), ()
+    if density is not None and free:
+        extent = float(density.scene_extent) if density.scene_extent is not None else scene_extent(c2w)
+        density.thresholds(extent)  # (a bad extent raises here, not at the first event)
+        densify_at, reset_at = density.events(int(iters))
+        stats = DensityStats(means.shape[0], dev)
+        noise_gen = torch.Generator(device=dev).manual_seed(int(density.seed))
+        unconstrained = {}  # the frozen fields in the form the density kernels read, made at the first event
     if free:
-        opt = torch.optim.Adam([{"params": [free[k]], "lr": lr[k]} for k in free], eps=1e-15, fused=True)
+        opt = new_adam()
         for it in range(int(iters)):
+            if it in densify_at:
+                for k in FIELDS:
+                    if k not in free and k not in unconstrained:
+                        unconstrained[k] = to_param[k](start[k])
+                state = {k: opt.state[free[k]] for k in free}
+                noise = torch.randn((stats.G, 2, 3), generator=noise_gen, device=dev, dtype=torch.float32)
+                new_p, new_m, info = densify_and_prune({k: (free[k].detach() if k in free else unconstrained[k]) for k in FIELDS},
+                                                       {k: (state[k]["exp_avg"], state[k]["exp_avg_sq"]) for k in free}, stats, density, extent, noise)
+                if info["rows_out"] == 0:
+                    raise RuntimeError(f"density control pruned every Gaussian at iteration {it}: {info}")
+                events.append(dict(info, iteration=it))
+                steps = {k: state[k]["step"] for k in free}  # (fused Adam: a device tensor per parameter)
+                free = {k: new_p[k].requires_grad_(True) for k in free}
+                for k in FIELDS:
+                    if k not in free:
+                        unconstrained[k] = new_p[k]
+                        start[k] = from_param[k](new_p[k])
+                opt = new_adam()
+                for k in free:
+                    opt.state[free[k]] = {"step": steps[k], "exp_avg": new_m[k][0], "exp_avg_sq": new_m[k][1]}
+                cov6_fixed = None if cov_moves else cov6_of()
+                stats = DensityStats(info["rows_out"], dev)
+            if it in reset_at and "opacities" in free:
+                with torch.no_grad():
+                    p = float(density.reset_opacity)
+                    free["opacities"].clamp_(max=math.log(p / (1.0 - p)))
+                    for m in ("exp_avg", "exp_avg_sq"):
+                        if m in opt.state[free["opacities"]]:
+                            opt.state[free["opacities"]][m].zero_()
             opt.zero_grad(set_to_none=True)
             cov6 = cov6_of() if cov_moves else cov6_fixed
             img, _ = render_cuda(c2w, Kn, near_t, far_t, (H, W), bg_t, value("means")[None].expand(V, -1, -1), cov6[None].expand(V, -1, -1),
-                                 value("harmonics")[None].expand(V, -1, -1, -1), value("opacities")[None].expand(V, -1))
+                                 value("harmonics")[None].expand(V, -1, -1, -1), value("opacities")[None].expand(V, -1), density_stats=stats)
             loss = photometric_loss(img, target, lambda_dssim)
             loss.backward()
             opt.step()
@@ -92,4 +146,6 @@ def refine_gaussians(means, scales, rotations, opacities, harmonics, images, c2w
     with torch.no_grad():
         out = {k: (value(k).detach().clone() if k in free else start[k].clone()) for k in FIELDS}
         out["covariances"] = covariances_from(out["rotations"], out["scales"])
+        if density is not None:
+            out["density_events"] = events
     return out, losses
