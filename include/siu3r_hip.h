@@ -197,6 +197,17 @@ int siu3r_attention(const siu3r_attn_params* p, void* stream);
 int siu3r_attention_kv_x3_ok(const siu3r_attn_params* p);
 
 /* ---- element-wise / gather kernels (see DESIGN.md for the HBM roofline of each) ---------- */
+/* Contract shared by the entry points of this section, siu3r_layernorm / siu3r_layernorm2 / siu3r_rope2d above and siu3r_split_bf16 below:
+ *  - EMPTY INPUT: a call whose element count is 0 (N = 0, rows = 0, n = 0, Q = 0, B = 0, ...) returns 0 without launching anything, after the
+ *    shape arguments have been validated; the data pointers are not looked at (an empty tensor's pointer may be null).
+ *  - ALIGNMENT: the kernels move four channels per lane.  The base pointers of the tensors they read or write that way -- x / y / addend of
+ *    resize, affine_add, the max-pools, dwconv3x3_gelu and groupnorm, a / b / y of add, value / out of msdeform_sample, y / y2 of the
+ *    LayerNorms -- must be 16-byte aligned for fp32 and 8-byte aligned for bf16; the fp32 x / gamma / beta of the LayerNorms, w9c of
+ *    dwconv3x3_gelu and out of pack_image_nhwc (one pixel per store) 16-byte aligned.  A misaligned pointer is refused (non-zero return, siu3r_last_error) before anything is launched.
+ *    C % 4 == 0 and the *_batch_stride % 4 == 0 / ld* % 4 == 0 rules keep every row aligned behind an aligned base.  Per-channel vectors read
+ *    one value at a time (ch_scale, ch_shift, bias, GroupNorm's gamma / beta) and the operands of pts3d_exp, m2f_attn_mask and
+ *    split_bf16 need only their natural alignment.  siu3r_gaussian_adapter and the offs_aw operand of siu3r_msdeform_sample take any
+ *    4-byte aligned pointer and use their 16-byte loads only when the pointer allows it. */
 /* y = a + b (b broadcast over rows when b_rows < rows: row r uses b[r % b_rows]) */
 int siu3r_add(const float* a, const float* b, float* y, int64_t rows, int64_t b_rows, int C, void* stream);
 /* image [N,3,H,W] fp32 (NCHW) -> [N,H,W,cpad] channel-last, zero padded channels: cpad = 8 (bf16 or fp32) or 4 (fp32: one 16-byte

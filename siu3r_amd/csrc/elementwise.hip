@@ -374,8 +374,9 @@ struct MsdShapes {
   int h[4], w[4], start[4];
 };
 // LT, PT > 0: levels / points known at compile time -- the softmax weights are computed once (the generic form evaluated every expf
-// twice), all loops unroll, the corner tests become weights (an out-of-range corner reads a clamped in-range texel with weight 0: same
-// sums, no divergent skips) and the compiler issues a point's four 16-byte gathers together.  LT = 0: any L <= 4, any P.
+// twice), all loops unroll, the corner tests become selects (an out-of-range corner reads a clamped in-range texel and replaces it by 0,
+// as grid_sample's zero padding and the generic form skip it: same sums, no divergent skips, and a non-finite texel reaches only the
+// samples that have it as an in-range corner) and the compiler issues a point's four 16-byte gathers together.  LT = 0: any L <= 4, any P.
 template <int LT, int PT>
 __global__ __launch_bounds__(256, 4) void msdeform_kernel(const void* value, int v_dtype, const float* offs_aw, const float* ref, MsdShapes sh,
                                                        void* out, int out_dtype, int B, int S, int Q, int heads, int d, int L, int P, int qb) {
@@ -458,7 +459,9 @@ __global__ __launch_bounds__(256, 4) void msdeform_kernel(const void* value, int
           const int xc = min(max(xx, 0), ww - 1), yc = min(max(yy, 0), hh - 1);
           const int s_ = st0 + yc * ww + xc;
           v[pt][k] = load4(value, v_dtype, ((vb + s_) * heads + hd) * d + dc);
-          wk[pt][k] = ok ? wgt[k] * aw : 0.f;
+#pragma unroll
+          for (int j = 0; j < 4; ++j) v[pt][k].v[j] = ok ? v[pt][k].v[j] : 0.f;  // (the VALUE is dropped, not its weight: 0 * inf = NaN)
+          wk[pt][k] = wgt[k] * aw;
         }
       }
 #pragma unroll
@@ -620,9 +623,10 @@ __global__ __launch_bounds__(256) void gaussian_adapter_kernel(const void* raw, 
   __shared__ float so[GA_ROWS * 17];  // per row: 3 scales, 4 rotations, 9 covariance entries (stride 17: conflict-free), copied out coalesced
   const int64_t g0 = (int64_t)blockIdx.x * GA_ROWS;
   const int rows = (int)((n - g0) < GA_ROWS ? (n - g0) : GA_ROWS);
-  // 256 threads move the rows (16 bytes per lane on full fp32 blocks: 128 x 83 floats start 16-byte aligned), 128 of them compute
+  // 256 threads move the rows (16 bytes per lane on full fp32 blocks: 128 x 83 floats = a multiple of 16 bytes, so every block starts as
+  // aligned as `raw` itself -- a view that begins at an odd row of a larger buffer is only 4-byte aligned), 128 of them compute
   const int nt = blockDim.x;
-  if (raw_dtype == SIU3R_F32 && rows == GA_ROWS) {
+  if (raw_dtype == SIU3R_F32 && rows == GA_ROWS && ((uintptr_t)raw & 15) == 0) {
     const float4* src = (const float4*)((const float*)raw + g0 * GA_D);
     for (int i = threadIdx.x; i < GA_ROWS * GA_D / 4; i += nt) ((float4*)s)[i] = src[i];
   } else {
@@ -678,7 +682,7 @@ __global__ __launch_bounds__(256) void gaussian_adapter_kernel(const void* raw, 
   for (int i = threadIdx.x; i < rows * 4; i += nt) rots[g0 * 4 + i] = so[(i >> 2) * 17 + 3 + (i & 3)];
   for (int i = threadIdx.x; i < rows * 9; i += nt) cov[g0 * 9 + i] = so[(i / 9) * 17 + 7 + i % 9];
   // harmonics: [n, 3, 25] = raw[:, 8:83] * mask[d_sh]
-  if (rows == GA_ROWS) {  // 128 x 75 floats: 16-byte aligned, a multiple of four
+  if (rows == GA_ROWS && ((uintptr_t)sh & 15) == 0) {  // 128 x 75 floats: a multiple of 16 bytes
     for (int i4 = threadIdx.x; i4 < GA_ROWS * GA_SH / 4; i4 += nt) {
       float v[4];
 #pragma unroll
@@ -758,6 +762,11 @@ __global__ void split_bf16_kernel(const float* x, u16* hi, u16* lo, u16* x3, int
 
 inline dim3 grid1d(int64_t total, int block = 256) { return dim3((unsigned)cdiv64(total, block)); }
 
+// base pointers of tensors that are read or written four elements per lane (load4 / store4 / float4): 16 bytes of fp32, 8 of bf16.
+// A null pointer passes (optional operands; required ones are null-checked by their entry point).
+inline bool al4(const void* p, int dtype) { return ((uintptr_t)p & (dtype == SIU3R_F32 ? 15 : 7)) == 0; }
+inline bool al16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
 }  // namespace
 
 // ================================ C ABI ==========================================================
@@ -784,9 +793,10 @@ extern "C" int siu3r_rope2d(void* tokens, int dtype, int B, int N, int H, int D,
 
 extern "C" int siu3r_layernorm(const float* x, void* y, int y_dtype, const float* gamma, const float* beta,
                                int64_t rows, int C, int64_t ldx, int64_t ldy, float eps, void* stream) {
-  SIU3R_CHECK(x && y && gamma && beta, "layernorm: null pointer");
   SIU3R_CHECK(C % 4 == 0 && C <= 2048 && ldx % 4 == 0 && ldy % 4 == 0, "layernorm: C=%d must be a multiple of 4 and <= 2048", C);
   if (rows == 0) return 0;
+  SIU3R_CHECK(x && y && gamma && beta, "layernorm: null pointer");
+  SIU3R_CHECK(al16(x) && al4(y, y_dtype) && al16(gamma) && al16(beta), "layernorm: x, gamma, beta must be 16-byte aligned, y 16 (fp32) / 8 (bf16)");
   hipLaunchKernelGGL(layernorm_kernel, dim3((unsigned)cdiv64(rows, 4)), dim3(256), 0, (hipStream_t)stream, x, y, y_dtype, (void*)nullptr, gamma, beta, rows, C, ldx, ldy, (int64_t)0, eps);
   SIU3R_LAUNCH_CHECK("siu3r_layernorm");
   return 0;
@@ -794,25 +804,31 @@ extern "C" int siu3r_layernorm(const float* x, void* y, int y_dtype, const float
 
 extern "C" int siu3r_layernorm2(const float* x, void* y, int y_dtype, void* y2_bf16, const float* gamma, const float* beta, int64_t rows,
                                 int C, int64_t ldx, int64_t ldy, int64_t ldy2, float eps, void* stream) {
-  SIU3R_CHECK(x && y && y2_bf16 && gamma && beta, "layernorm2: null pointer");
   SIU3R_CHECK(C % 4 == 0 && C <= 2048 && ldx % 4 == 0 && ldy % 4 == 0 && ldy2 % 4 == 0, "layernorm2: C=%d must be a multiple of 4 and <= 2048", C);
   if (rows == 0) return 0;
+  SIU3R_CHECK(x && y && y2_bf16 && gamma && beta, "layernorm2: null pointer");
+  SIU3R_CHECK(al16(x) && al4(y, y_dtype) && al4(y2_bf16, SIU3R_BF16) && al16(gamma) && al16(beta),
+              "layernorm2: x, gamma, beta must be 16-byte aligned, y 16 (fp32) / 8 (bf16), y2 8");
   hipLaunchKernelGGL(layernorm_kernel, dim3((unsigned)cdiv64(rows, 4)), dim3(256), 0, (hipStream_t)stream, x, y, y_dtype, y2_bf16, gamma, beta, rows, C, ldx, ldy, ldy2, eps);
   SIU3R_LAUNCH_CHECK("siu3r_layernorm2");
   return 0;
 }
 
 extern "C" int siu3r_add(const float* a, const float* b, float* y, int64_t rows, int64_t b_rows, int C, void* stream) {
-  SIU3R_CHECK(a && b && y && C % 4 == 0 && b_rows > 0, "add: bad arguments");
-  if (rows == 0) return 0;
+  SIU3R_CHECK(C % 4 == 0 && b_rows > 0, "add: bad arguments");
+  if (rows == 0 || C == 0) return 0;
+  SIU3R_CHECK(a && b && y, "add: null pointer");
+  SIU3R_CHECK(al16(a) && al16(b) && al16(y), "add: a, b, y must be 16-byte aligned");
   hipLaunchKernelGGL(add_kernel, grid1d(rows * (C / 4)), dim3(256), 0, (hipStream_t)stream, a, b, y, rows, b_rows, C / 4);
   SIU3R_LAUNCH_CHECK("siu3r_add");
   return 0;
 }
 
 extern "C" int siu3r_pack_image_nhwc(const float* img, void* out, int out_dtype, int N, int H, int W, int cpad, void* stream) {
-  SIU3R_CHECK(img && out, "pack_image: null pointer");
   SIU3R_CHECK(cpad == 8 || (cpad == 4 && out_dtype == SIU3R_F32), "pack_image: 8 channels (bf16 / fp32) or 4 channels (fp32) per pixel, got %d", cpad);
+  if ((int64_t)N * H * W == 0) return 0;
+  SIU3R_CHECK(img && out, "pack_image: null pointer");
+  SIU3R_CHECK(al16(out), "pack_image: out must be 16-byte aligned");
   hipLaunchKernelGGL(pack_image_kernel, grid1d((int64_t)N * H * W), dim3(256), 0, (hipStream_t)stream, img, out, out_dtype, N, H, W, cpad);
   SIU3R_LAUNCH_CHECK("siu3r_pack_image_nhwc");
   return 0;
@@ -821,8 +837,11 @@ extern "C" int siu3r_pack_image_nhwc(const float* img, void* out, int out_dtype,
 extern "C" int siu3r_resize_bilinear_strided(const void* x, int x_dtype, void* y, int y_dtype, const void* addend, int add_dtype,
                                              const float* ch_scale, const float* ch_shift, int N, int IH, int IW, int OH, int OW, int C,
                                              int align_corners, int64_t x_batch_stride, int64_t addend_batch_stride, void* stream) {
-  SIU3R_CHECK(x && y && C % 4 == 0, "resize_bilinear: bad arguments (C=%d)", C);
+  SIU3R_CHECK(C % 4 == 0, "resize_bilinear: bad arguments (C=%d)", C);
   SIU3R_CHECK((ch_scale == nullptr) == (ch_shift == nullptr), "resize_bilinear: scale/shift must come together");
+  if ((int64_t)N * OH * OW * C == 0) return 0;
+  SIU3R_CHECK(x && y && IH > 0 && IW > 0, "resize_bilinear: null pointer or empty source");
+  SIU3R_CHECK(al4(x, x_dtype) && al4(y, y_dtype) && al4(addend, add_dtype), "resize_bilinear: x, y, addend must be 16-byte (fp32) / 8-byte (bf16) aligned");
   SIU3R_CHECK(x_batch_stride >= (int64_t)IH * IW * C && x_batch_stride % 4 == 0 && (!addend || (addend_batch_stride >= (int64_t)OH * OW * C && addend_batch_stride % 4 == 0)),
               "resize_bilinear: batch strides must cover one map and keep 4-element alignment");
   hipLaunchKernelGGL(resize_kernel, grid1d((int64_t)N * OH * OW * (C / 4)), dim3(256), 0, (hipStream_t)stream, x, x_dtype, y, y_dtype, addend, add_dtype, ch_scale, ch_shift, N, IH, IW, OH, OW, C, align_corners, x_batch_stride, addend_batch_stride);
@@ -840,7 +859,10 @@ extern "C" int siu3r_resize_bilinear(const void* x, int x_dtype, void* y, int y_
 extern "C" int siu3r_affine_add_strided(const void* x, int x_dtype, const void* addend, int add_dtype, void* y, int y_dtype, const float* ch_scale,
                                         const float* ch_shift, int64_t rows, int C, int64_t rows_per_batch, int64_t x_batch_stride,
                                         int64_t addend_batch_stride, void* stream) {
-  SIU3R_CHECK(x && y && C % 4 == 0 && rows_per_batch > 0 && rows % rows_per_batch == 0, "affine_add: bad arguments");
+  SIU3R_CHECK(C % 4 == 0, "affine_add: bad arguments");
+  if (rows == 0 || C == 0) return 0;
+  SIU3R_CHECK(x && y && rows_per_batch > 0 && rows % rows_per_batch == 0, "affine_add: bad arguments");
+  SIU3R_CHECK(al4(x, x_dtype) && al4(y, y_dtype) && al4(addend, add_dtype), "affine_add: x, y, addend must be 16-byte (fp32) / 8-byte (bf16) aligned");
   SIU3R_CHECK(x_batch_stride >= rows_per_batch * C && x_batch_stride % 4 == 0 && (!addend || (addend_batch_stride >= rows_per_batch * C && addend_batch_stride % 4 == 0)),
               "affine_add: batch strides must cover one batch item and keep 4-element alignment");
   hipLaunchKernelGGL(affine_add_kernel, grid1d(rows * (C / 4)), dim3(256), 0, (hipStream_t)stream, x, x_dtype, addend, add_dtype, y, y_dtype, ch_scale, ch_shift, rows, C,
@@ -855,7 +877,10 @@ extern "C" int siu3r_affine_add(const void* x, int x_dtype, const void* addend, 
 }
 
 extern "C" int siu3r_maxpool3x3s2(const void* x, void* y, int dtype, int N, int IH, int IW, int C, void* stream) {
-  SIU3R_CHECK(x && y && C % 4 == 0, "maxpool: bad arguments");
+  SIU3R_CHECK(C % 4 == 0, "maxpool: bad arguments");
+  if ((int64_t)N * IH * IW * C == 0) return 0;
+  SIU3R_CHECK(x && y, "maxpool: null pointer");
+  SIU3R_CHECK(al4(x, dtype) && al4(y, dtype), "maxpool: x, y must be 16-byte (fp32) / 8-byte (bf16) aligned");
   const int OH = (IH + 2 - 3) / 2 + 1, OW = (IW + 2 - 3) / 2 + 1;
   hipLaunchKernelGGL(maxpool_kernel, grid1d((int64_t)N * OH * OW * (C / 4)), dim3(256), 0, (hipStream_t)stream, x, y, dtype, N, IH, IW, OH, OW, C);
   SIU3R_LAUNCH_CHECK("siu3r_maxpool3x3s2");
@@ -863,7 +888,10 @@ extern "C" int siu3r_maxpool3x3s2(const void* x, void* y, int dtype, int N, int 
 }
 
 extern "C" int siu3r_maxpool2x2s2(const void* x, void* y, int dtype, int N, int IH, int IW, int C, void* stream) {
-  SIU3R_CHECK(x && y && C % 4 == 0 && IH >= 2 && IW >= 2, "maxpool2x2s2: bad arguments");
+  SIU3R_CHECK(C % 4 == 0 && IH >= 2 && IW >= 2, "maxpool2x2s2: bad arguments");
+  if ((int64_t)N * C == 0) return 0;
+  SIU3R_CHECK(x && y, "maxpool2x2s2: null pointer");
+  SIU3R_CHECK(al4(x, dtype) && al4(y, dtype), "maxpool2x2s2: x, y must be 16-byte (fp32) / 8-byte (bf16) aligned");
   const int OH = IH / 2, OW = IW / 2;
   hipLaunchKernelGGL(maxpool2x2_kernel, grid1d((int64_t)N * OH * OW * (C / 4)), dim3(256), 0, (hipStream_t)stream, x, y, dtype, N, IH, IW, OH, OW, C);
   SIU3R_LAUNCH_CHECK("siu3r_maxpool2x2s2");
@@ -880,8 +908,11 @@ extern "C" int siu3r_lpips_layer(const float* f0, const float* f1, const float* 
 
 extern "C" int siu3r_dwconv3x3_gelu(const void* x, void* y, int dtype, const float* w9c, const float* bias, int B,
                                     int H, int W, int C, void* stream) {
-  SIU3R_CHECK(x && y && w9c && bias && C % 4 == 0 && H % 2 == 0 && W % 2 == 0, "dwconv3x3_gelu: bad arguments");
+  SIU3R_CHECK(C % 4 == 0 && H % 2 == 0 && W % 2 == 0, "dwconv3x3_gelu: bad arguments");
   const int64_t ntok = 21 * (int64_t)(H * W / 4);
+  if ((int64_t)B * ntok * C == 0) return 0;
+  SIU3R_CHECK(x && y && w9c && bias, "dwconv3x3_gelu: null pointer");
+  SIU3R_CHECK(al4(x, dtype) && al4(y, dtype) && al16(w9c), "dwconv3x3_gelu: x, y must be 16-byte (fp32) / 8-byte (bf16) aligned, w9c 16");
   hipLaunchKernelGGL(dwconv_gelu_kernel, grid1d((int64_t)B * ntok * (C / 4)), dim3(256), 0, (hipStream_t)stream, x, y, dtype, w9c, bias, B, H, W, C);
   SIU3R_LAUNCH_CHECK("siu3r_dwconv3x3_gelu");
   return 0;
@@ -890,7 +921,7 @@ extern "C" int siu3r_dwconv3x3_gelu(const void* x, void* y, int dtype, const flo
 extern "C" int siu3r_msdeform_sample(const void* value, int v_dtype, const float* offs_aw, const float* ref,
                                      const int32_t* shapes_host, void* out, int out_dtype, int B, int S, int Q,
                                      int heads, int d, int L, int P, void* stream) {
-  SIU3R_CHECK(value && offs_aw && ref && shapes_host && out, "msdeform_sample: null pointer");
+  SIU3R_CHECK(shapes_host, "msdeform_sample: null pointer");
   SIU3R_CHECK(L >= 1 && L <= 4 && d % 4 == 0, "msdeform_sample: L=%d (1..4), d=%d (%%4)", L, d);
   MsdShapes sh;
   int start = 0;
@@ -901,6 +932,9 @@ extern "C" int siu3r_msdeform_sample(const void* value, int v_dtype, const float
     start += sh.h[l] * sh.w[l];
   }
   SIU3R_CHECK(start == S, "msdeform_sample: spatial shapes sum %d != S=%d", start, S);
+  if ((int64_t)B * Q * heads * d == 0) return 0;
+  SIU3R_CHECK(value && offs_aw && ref && out, "msdeform_sample: null pointer");
+  SIU3R_CHECK(al4(value, v_dtype) && al4(out, out_dtype), "msdeform_sample: value, out must be 16-byte (fp32) / 8-byte (bf16) aligned");
   const int D4 = d / 4;
   const int qb = (256 % D4 == 0) ? 256 / D4 : 0;  // queries per workgroup (0: the flat thread order)
   const dim3 grid = qb ? dim3((unsigned)((int64_t)B * ((Q + qb - 1) / qb) * heads)) : grid1d((int64_t)B * Q * heads * D4);
@@ -918,8 +952,10 @@ extern "C" int siu3r_msdeform_sample(const void* value, int v_dtype, const float
 extern "C" int siu3r_groupnorm(const void* x, int x_dtype, void* y, int y_dtype, const float* gamma,
                                const float* beta, float* stats_ws, const void* addend, int add_dtype, int relu, int N,
                                int HW, int C, int groups, float eps, void* stream) {
+  SIU3R_CHECK(groups > 0 && C % groups == 0 && (C / groups) % 4 == 0, "groupnorm: C/groups must be a multiple of 4");
+  if ((int64_t)N * HW * C == 0) return 0;
   SIU3R_CHECK(x && y && gamma && beta && stats_ws, "groupnorm: null pointer");
-  SIU3R_CHECK(C % groups == 0 && (C / groups) % 4 == 0, "groupnorm: C/groups must be a multiple of 4");
+  SIU3R_CHECK(al4(x, x_dtype) && al4(y, y_dtype) && al4(addend, add_dtype), "groupnorm: x, y, addend must be 16-byte (fp32) / 8-byte (bf16) aligned");
   hipStream_t s = (hipStream_t)stream;
   hipLaunchKernelGGL(gn_stats_kernel, dim3(groups, N), dim3(GN_T), 0, s, x, x_dtype, stats_ws, HW, C, groups, eps);
   hipLaunchKernelGGL(gn_apply_kernel, grid1d((int64_t)N * HW * (C / 4)), dim3(256), 0, s, x, x_dtype, y, y_dtype, gamma, beta, stats_ws, addend, add_dtype, relu, N, HW, C, groups);
@@ -928,6 +964,7 @@ extern "C" int siu3r_groupnorm(const void* x, int x_dtype, void* y, int y_dtype,
 }
 
 extern "C" int siu3r_pts3d_exp(float* xyz, int64_t n, void* stream) {
+  if (n == 0) return 0;
   SIU3R_CHECK(xyz, "pts3d_exp: null pointer");
   hipLaunchKernelGGL(pts3d_kernel, grid1d(n), dim3(256), 0, (hipStream_t)stream, xyz, n);
   SIU3R_LAUNCH_CHECK("siu3r_pts3d_exp");
@@ -937,6 +974,7 @@ extern "C" int siu3r_pts3d_exp(float* xyz, int64_t n, void* stream) {
 extern "C" int siu3r_gaussian_adapter(const void* raw, int raw_dtype, float* opacities, float* scales,
                                       float* rotations, float* harmonics, float* covariances, int64_t n,
                                       void* stream) {
+  if (n == 0) return 0;
   SIU3R_CHECK(raw && opacities && scales && rotations && harmonics && covariances, "gaussian_adapter: null pointer");
   static bool mask_set = false;
   if (!mask_set) {
@@ -960,8 +998,9 @@ extern "C" int siu3r_gaussian_adapter(const void* raw, int raw_dtype, float* opa
 
 extern "C" int siu3r_m2f_attn_mask(const float* mask_logits, uint8_t* out, int32_t* row_counts_ws, int B, int T,
                                    int IH, int IW, int OH, int OW, int Q, int64_t out_ld, void* stream) {
-  SIU3R_CHECK(mask_logits && out && row_counts_ws, "m2f_attn_mask: null pointer");
   SIU3R_CHECK(out_ld >= (int64_t)T * OH * OW, "m2f_attn_mask: out_ld too small");
+  if ((int64_t)B * Q * T * OH * OW == 0) return 0;
+  SIU3R_CHECK(mask_logits && out && row_counts_ws && IH > 0 && IW > 0, "m2f_attn_mask: null pointer or empty source");
   hipStream_t s = (hipStream_t)stream;
   // (a kernel, not hipMemsetAsync: inside a captured per-chain graph the memset node was observed not to be ordered before the
   // counting kernel on replay -- stale counts from the previous replay survived)
@@ -975,8 +1014,9 @@ extern "C" int siu3r_m2f_attn_mask(const float* mask_logits, uint8_t* out, int32
 
 extern "C" int siu3r_split_bf16(const float* x, void* hi, void* lo, void* x3, int64_t rows, int k, int kpad, int64_t ldx,
                                 void* stream) {
-  SIU3R_CHECK(x && (hi || x3) && kpad >= k && (!x3 || kpad % 32 == 0), "split_bf16: bad arguments");
-  if (rows == 0) return 0;
+  SIU3R_CHECK(kpad >= k && (!x3 || kpad % 32 == 0), "split_bf16: bad arguments");
+  if (rows == 0 || kpad == 0) return 0;
+  SIU3R_CHECK(x && (hi || x3), "split_bf16: null pointer");
   hipLaunchKernelGGL(split_bf16_kernel, grid1d(rows * kpad), dim3(256), 0, (hipStream_t)stream, x, (u16*)hi, (u16*)lo, (u16*)x3, rows, k, kpad, ldx);
   SIU3R_LAUNCH_CHECK("siu3r_split_bf16");
   return 0;

@@ -5,6 +5,7 @@ arithmetic operation below runs in libsiu3r_hip.so.  No CPU fallback: non-GPU te
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 from dataclasses import dataclass
 from typing import Optional, Sequence
@@ -913,7 +914,7 @@ def affine_add(x: torch.Tensor, addend, ch_scale, ch_shift, out_dtype=None):
     """y = x * scale[c] + shift[c] (+ addend); x / addend [N, ..., C] dense or batch-strided views (see resize_bilinear)."""
     _gpu(x, addend)
     Cc = x.shape[-1]
-    rows_pb = x[0].numel() // Cc
+    rows_pb = math.prod(x.shape[1:-1])
     x_bs = _batch_strided(x, rows_pb * Cc)
     a_bs = rows_pb * Cc
     if addend is not None:
@@ -986,7 +987,7 @@ def groupnorm(x: torch.Tensor, gamma, beta, groups=32, eps=1e-5, *, relu=False, 
     _gpu(x, addend)
     assert x.is_contiguous()
     N, Cc = x.shape[0], x.shape[-1]
-    HW = x.numel() // (N * Cc)
+    HW = math.prod(x.shape[1:-1])
     out = torch.empty(x.shape, dtype=out_dtype or x.dtype, device=x.device)
     ws = torch.empty((N, groups, 2), dtype=torch.float32, device=x.device)
     check(_lib.lib().siu3r_groupnorm(_p(x), _dt(x), _p(out), _dt(out), _p(gamma), _p(beta), _p(ws), _p(addend),
