@@ -500,6 +500,23 @@ int siu3r_photo_loss(const float* pred, const float* target, int V, int C, int H
                      const int64_t* target_strides, float lambda, float data_range, float* grad_pred, float* partials, float* out,
                      void* stream);
 
+/* ---- depth loss of splat refinement (csrc/depth_loss.hip): value and gradient w.r.t. the K2 render's depth and opacity ----
+ * depth (D = sum w z), opacity (O = sum w), target (T), weight (Wt, or NULL = 1): fp32 [V,H,W], contiguous, on the device.
+ * A pixel is valid iff O > min_opacity, D > 0, T > 0, Wt > 0 and all four are finite (a NaN fails every comparison); an invalid pixel
+ * adds nothing to any sum and gets +0 in both gradient maps.  space 0: x = D / O against y = T; space 1: x = O / D against y = 1 / T.
+ * mode 0 (l1): loss = sum w |x - y| / N, N = sum w over the valid pixels of all views (N = 0: loss 0); out = (loss, N, 1 / N or 0, 0);
+ *   per_view [V] = the view's sum w |x - y| / sum w (NaN without a valid pixel).  g_depth / g_opacity are written WITHOUT the factor 1 / N:
+ *   d loss / d depth = g_depth * out[2] (one pass; the caller folds out[2] into the multiply with its upstream gradient).
+ * mode 1 (pearson): per view rho of the w-weighted (x, y) over its valid pixels; a view counts iff it has >= 2 valid pixels, max x > min x
+ *   and max y > min y; loss = mean of 1 - rho over the counted views (none: 0); out = (loss, counted views, 1, 0); per_view [V] = 1 - rho
+ *   (NaN for a view that is not counted); g_depth / g_opacity are the full derivative (zero in a view that is not counted).
+ * valid [V] int32: the exact number of valid pixels per view.  g_depth, g_opacity: both [V,H,W] (every pixel is written) or both NULL.
+ * ws: siu3r_depth_loss_ws(V, H, W) BYTES of workspace, 8-byte aligned (0: the shape is not supported).  H * W < 2^31 - 1024, V <= 65535,
+ * min_opacity >= 0.  Deterministic (fixed-order fp64 sums, no atomics); nothing allocates or synchronises with the host. */
+int64_t siu3r_depth_loss_ws(int V, int H, int W);
+int siu3r_depth_loss(const float* depth, const float* opacity, const float* target, const float* weight, int V, int H, int W, int mode, int space,
+                     float min_opacity, float* g_depth, float* g_opacity, void* ws, float* out, float* per_view, int32_t* valid, void* stream);
+
 /* ---- adaptive density control of splat refinement (csrc/density.hip; Kerbl et al. 2023, section 5.2): clone / split / prune ----
  * Deterministic (no float atomics; two calls on the same input give the same bits), nothing allocates or synchronises with the host.
  * Statistics, every iteration.  g_mean2d [V,G,2]: the pixel-space mean gradient as siu3r_raster_project_bwd writes it (rows of culled

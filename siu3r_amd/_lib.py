@@ -147,6 +147,8 @@ SIGNATURES = {
     "siu3r_sh_eval_bwd": [_P, _P, _P, _I, _I, _P, _P, _P, _P, _L, _P],
     "siu3r_photo_loss_partials": [_I, _I, _I, _I],
     "siu3r_photo_loss": [_P, _P, _I, _I, _I, _I, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _F, _F, _P, _P, _P, _P],
+    "siu3r_depth_loss_ws": [_I, _I, _I],
+    "siu3r_depth_loss": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _P, _P, _P, _P, _P, _P, _P],
     "siu3r_density_accumulate": [_P, _P, _I, _L, _F, _F, _P, _P, _P, _P],
     "siu3r_density_plan_ws": [_L],
     "siu3r_density_plan": [_P, _P, _P, _P, _P, _L, _F, _F, _F, _I, _F, _I, _P, _P, _P, _P, _P],
@@ -158,6 +160,7 @@ SIGNATURES = {
 _RESTYPES = {"siu3r_last_error": C.c_char_p, "siu3r_raster_composite_feat_ws_bytes": C.c_int64, "siu3r_raster_pose_partial_rows": C.c_int64}
 _RESTYPES["siu3r_photo_loss_partials"] = C.c_int64
 _RESTYPES["siu3r_density_plan_ws"] = C.c_int64
+_RESTYPES["siu3r_depth_loss_ws"] = C.c_int64
 
 _lib = None
 

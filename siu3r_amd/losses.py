@@ -5,11 +5,14 @@ SSIM is `metrics.ssim` with an explicit data_range (separable 11-tap Gaussian wi
 averaged over the valid (H - 10) x (W - 10) region, then over channels and views); L1 is the mean of |pred - target| over everything.
 Images are read as stored: [V, C, H, W] (the K2 render), [V, H, W, C] with channels_last=True (the gsplat seam), sliced views of either;
 only a layout the kernel's four strides cannot express (an expanded dimension of a differentiated `pred`) costs a `.contiguous()`.
+
+`depth_loss` is the depth term of the same refinement (csrc/depth_loss.hip): weighted L1 or per-view Pearson correlation of the K2 render's
+depth / opacity against a target depth, value and the gradients w.r.t. both render outputs from one call.
 There is no CPU path and nothing here synchronises with the host."""
 from __future__ import annotations
 
 import ctypes as C
-from typing import Tuple
+from typing import Optional, Tuple
 
 import torch
 
@@ -138,3 +141,109 @@ def ssim(pred: torch.Tensor, target: torch.Tensor, data_range: float = 1.0, chan
 def l1(pred: torch.Tensor, target: torch.Tensor) -> torch.Tensor:
     """mean |pred - target| over everything as a 0-d device tensor (differentiable w.r.t. `pred`); any of the layouts above"""
     return photometric_loss(pred, target, 0.0)
+
+
+# ---- depth loss (csrc/depth_loss.hip, DESIGN.md section 11) ----------------------------------------------------------------------------
+DEPTH_MODES = {"l1": 0, "pearson": 1}
+DEPTH_SPACES = {"depth": 0, "inverse": 1}
+
+
+def _check_depth(depth, opacity, target, weight, mode, space, min_opacity):
+    if mode not in DEPTH_MODES:
+        raise ValueError(f"mode must be one of {tuple(DEPTH_MODES)}, got {mode!r}")
+    if space not in DEPTH_SPACES:
+        raise ValueError(f"space must be one of {tuple(DEPTH_SPACES)}, got {space!r}")
+    if not 0.0 <= min_opacity < float("inf"):
+        raise ValueError(f"min_opacity must be finite and >= 0, got {min_opacity}")
+    named = [("depth", depth), ("opacity", opacity), ("target", target)] + ([("weight", weight)] if weight is not None else [])
+    for name, t in named:
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name} must be a tensor, got {type(t).__name__}")
+    _gpu(*(t for _, t in named))
+    if depth.dim() not in (2, 3) or depth.numel() == 0:
+        raise ValueError(f"depth must be [V,H,W] or one [H,W] image, got {tuple(depth.shape)}")
+    for name, t in named:
+        if t.dtype != torch.float32:
+            raise ValueError(f"the depth loss takes float32 maps, {name} is {t.dtype}")
+        if t.shape != depth.shape:
+            raise ValueError(f"depth {tuple(depth.shape)} and {name} {tuple(t.shape)} differ in shape")
+        if t.device != depth.device:
+            raise ValueError(f"depth is on {depth.device}, {name} on {t.device}")
+
+
+def _launch_depth(depth3, opacity3, target3, weight3, mode: str, space: str, min_opacity: float, want_grad: bool):
+    """One siu3r_depth_loss call on contiguous [V,H,W] maps.  Returns (out [4] = loss, N or counted views, the factor the gradient maps
+    still owe, 0; per_view [V]; valid [V] int32; g_depth, g_opacity or None, None)."""
+    lib = _lib.lib()
+    V, H, W = depth3.shape
+    dev = depth3.device
+    nbytes = int(lib.siu3r_depth_loss_ws(V, H, W))
+    if nbytes <= 0:
+        raise ValueError(f"depth maps {tuple(depth3.shape)} are too large for the depth loss kernel")
+    ws = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+    out = torch.empty(4, dtype=torch.float32, device=dev)
+    per_view = torch.empty(V, dtype=torch.float32, device=dev)
+    valid = torch.empty(V, dtype=torch.int32, device=dev)
+    gd = torch.empty_like(depth3) if want_grad else None
+    go = torch.empty_like(depth3) if want_grad else None
+    with torch.cuda.device(dev):
+        check(lib.siu3r_depth_loss(_p(depth3), _p(opacity3), _p(target3), _p(weight3), V, H, W, DEPTH_MODES[mode], DEPTH_SPACES[space],
+                                   float(min_opacity), _p(gd), _p(go), _p(ws), _p(out), _p(per_view), _p(valid), _stream()))
+    return out, per_view, valid, gd, go
+
+
+def _as_vhw(x: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
+    """contiguous [V,H,W] storage of a [V,H,W] / [H,W] map, detached (a copy only where the input is not contiguous)"""
+    if x is None:
+        return None
+    x = x.detach()
+    return (x.unsqueeze(0) if x.dim() == 2 else x).contiguous()
+
+
+class _DepthLoss(torch.autograd.Function):
+    """The fused kernel: the forward call already produces d loss / d depth and d loss / d opacity for a loss gradient of 1 (mode l1: up
+    to the device scalar 1 / N), the backward is one multiply per map."""
+
+    @staticmethod
+    def forward(ctx, depth, opacity, target, weight, mode, space, min_opacity):
+        out, per_view, valid, gd, go = _launch_depth(_as_vhw(depth), _as_vhw(opacity), _as_vhw(target), _as_vhw(weight), mode, space, min_opacity, True)
+        ctx.save_for_backward(gd, go, out[2])
+        ctx.shape = depth.shape
+        ctx.mark_non_differentiable(per_view, valid)
+        return out[0], per_view, valid
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_loss, _g_per_view, _g_valid):
+        gd, go, owed = ctx.saved_tensors
+        s = g_loss * owed
+        g_depth = (gd * s).reshape(ctx.shape) if ctx.needs_input_grad[0] else None
+        g_opacity = (go * s).reshape(ctx.shape) if ctx.needs_input_grad[1] else None
+        return g_depth, g_opacity, None, None, None, None, None
+
+
+def depth_loss(depth: torch.Tensor, opacity: torch.Tensor, target: torch.Tensor, weight: Optional[torch.Tensor] = None, mode: str = "l1",
+               space: str = "depth", min_opacity: float = 0.5, return_terms: bool = False):
+    """Depth term of splat refinement on the K2 render's own outputs, as a 0-d device tensor: `depth` is the render's sum w z, `opacity` its
+    sum w, `target` the depth to match, `weight` an optional per-pixel confidence; all float32 [V,H,W] (or one [H,W] image) on the GPU.
+
+    A pixel is valid iff opacity > min_opacity, depth > 0, target > 0, weight > 0 and all of them are finite (a NaN or an infinity makes
+    the pixel invalid); an invalid pixel contributes nothing and receives a zero gradient.  space="depth" compares the expected depth
+    depth / opacity with the target, space="inverse" compares opacity / depth with 1 / target.
+    mode="l1" (a metric target: sensor depth, an earlier render): sum w |x - y| / sum w over the valid pixels of all views; no valid pixel
+    gives 0.  mode="pearson" (a monocular prior, invariant to scale and shift): the mean over the counted views of 1 - rho_v, rho_v the
+    weighted Pearson correlation of the view's valid pixels; a view counts when it has at least two valid pixels and neither x nor y is
+    constant over them; no counted view gives 0.
+
+    Differentiable w.r.t. `depth` and `opacity` (the subgradient of |x| at 0 is 0); `target` and `weight` receive no gradient.
+    return_terms: (loss, per_view [V], valid [V] int32), the last two detached: per view the l1 mean or 1 - rho_v (NaN where the view has
+    nothing to report) and the exact count of valid pixels.  Non-contiguous inputs cost a `.contiguous()`.  There is no CPU path, and
+    nothing here synchronises with the host."""
+    min_opacity = float(min_opacity)
+    _check_depth(depth, opacity, target, weight, mode, space, min_opacity)
+    if torch.is_grad_enabled() and (depth.requires_grad or opacity.requires_grad):
+        loss, per_view, valid = _DepthLoss.apply(depth, opacity, target, weight, mode, space, min_opacity)
+    else:
+        out, per_view, valid, _, _ = _launch_depth(_as_vhw(depth), _as_vhw(opacity), _as_vhw(target), _as_vhw(weight), mode, space, min_opacity, False)
+        loss = out[0]
+    return (loss, per_view, valid) if return_terms else loss

@@ -12,7 +12,7 @@ import torch
 from . import raster
 from .cuda_splatting import render_cuda
 from .density import DensityControl, DensityStats, densify_and_prune, scene_extent
-from .losses import photometric_loss
+from .losses import DEPTH_MODES, DEPTH_SPACES, depth_loss, photometric_loss
 
 FIELDS = ("means", "scales", "rotations", "opacities", "harmonics")
 # Adam steps per field, those of the 3DGS training recipe (Kerbl et al. 2023): position 1.6e-4 (there times the scene extent, and decayed),
@@ -27,9 +27,57 @@ def covariances_from(rotations_xyzw: torch.Tensor, scales: torch.Tensor) -> torc
     return cov6[:, list(_COV33)].view(-1, 3, 3)
 
 
+def depth_weight_schedule(lambda_depth, iters: int) -> List[float]:
+    """The weight of the depth term at every iteration.  A float is constant; a (start, end) pair of positive numbers decays exponentially,
+    lambda_t = start * (end / start) ** (t / (iters - 1)) with both endpoints exact (the schedule of 3DGS's depth regulariser);
+    iters == 1 gives [start]."""
+    n = max(int(iters), 0)
+    if isinstance(lambda_depth, (tuple, list)):
+        if len(lambda_depth) != 2:
+            raise ValueError(f"lambda_depth must be a number or a (start, end) pair, got {lambda_depth!r}")
+        a, b = float(lambda_depth[0]), float(lambda_depth[1])
+        if not (0.0 < a < math.inf and 0.0 < b < math.inf):
+            raise ValueError(f"lambda_depth (start, end) must both be positive and finite, got {lambda_depth!r}")
+        if n <= 1:
+            return [a] * n
+        return [a] + [a * (b / a) ** (t / (n - 1)) for t in range(1, n - 1)] + [b]
+    lam = float(lambda_depth)
+    if not math.isfinite(lam):
+        raise ValueError(f"lambda_depth must be finite, got {lambda_depth!r}")
+    return [lam] * n
+
+
+def _check_depth_args(images, depths, depth_weights, lambda_depth, depth_mode, depth_space, depth_min_opacity, iters) -> Optional[List[float]]:
+    """host-side validation of refine_gaussians' depth keywords, before any device work; the schedule, or None when the term is off"""
+    schedule = depth_weight_schedule(lambda_depth, iters)
+    off = not isinstance(lambda_depth, (tuple, list)) and float(lambda_depth) == 0.0
+    if depths is None:
+        if not off:
+            raise ValueError("lambda_depth is non-zero but no `depths` were given")
+        if depth_weights is not None:
+            raise ValueError("depth_weights without `depths`")
+        return None
+    if depth_mode not in DEPTH_MODES:
+        raise ValueError(f"depth_mode must be one of {tuple(DEPTH_MODES)}, got {depth_mode!r}")
+    if depth_space not in DEPTH_SPACES:
+        raise ValueError(f"depth_space must be one of {tuple(DEPTH_SPACES)}, got {depth_space!r}")
+    if not 0.0 <= float(depth_min_opacity) < math.inf:
+        raise ValueError(f"depth_min_opacity must be finite and >= 0, got {depth_min_opacity}")
+    want = (images.shape[0], images.shape[-2], images.shape[-1])
+    for name, t in (("depths", depths), ("depth_weights", depth_weights)):
+        if t is None:
+            continue
+        if not isinstance(t, torch.Tensor) or tuple(t.shape) != want:
+            raise ValueError(f"{name} must be a [V,H,W] tensor matching images: expected {want}, got {tuple(getattr(t, 'shape', ()))}")
+    if depth_weights is not None and bool((depth_weights < 0).any()):  # (device weights: the one host read of the depth keywords)
+        raise ValueError("depth_weights must be >= 0")
+    return None if off else schedule
+
+
 def refine_gaussians(means, scales, rotations, opacities, harmonics, images, c2w, Kn, near, far, bg, iters: int = 200, lambda_dssim: float = 0.2,
                      lrs: Optional[Dict[str, float]] = None, params: Sequence[str] = FIELDS, log_every: int = 1,
-                     density: Optional[DensityControl] = None) -> Tuple[Dict[str, torch.Tensor], List[float]]:
+                     density: Optional[DensityControl] = None, depths=None, depth_weights=None, lambda_depth=0.0, depth_mode: str = "l1",
+                     depth_space: str = "depth", depth_min_opacity: float = 0.5) -> Tuple[Dict[str, torch.Tensor], List[float]]:
     """means [G,3], scales [G,3], rotations [G,4], opacities [G], harmonics [G,3,n] (n = (deg+1)^2): what `Gaussians` carries, on the GPU.
     images [V,3,H,W]: the posed target views; c2w [V,4,4] camera-to-world, Kn [V,3,3] (or [3,3]) normalised intrinsics, near / far floats
     (or [V]), bg 3 floats: render_cuda's conventions.
@@ -57,7 +105,16 @@ def refine_gaussians(means, scales, rotations, opacities, harmonics, images, c2w
     frozen scales / opacities make one round trip through log / logit at the first event.  An opacity reset clamps the free logit
     opacities to at most logit(control.reset_opacity) and zeroes their moments (frozen opacities could never recover and are left
     alone).  Every returned tensor then has the new row count, and the dict gains "density_events": one info dict per event
-    (densify_and_prune's counts plus "iteration").  control.scene_extent = None costs one host read of the camera centres."""
+    (densify_and_prune's counts plus "iteration").  control.scene_extent = None costs one host read of the camera centres.
+
+    depths [V,H,W] with a non-zero lambda_depth adds a depth term: the objective of iteration t is photometric + lambda_t *
+    losses.depth_loss(render depth, render opacity, depths, depth_weights, depth_mode, depth_space, depth_min_opacity) on the same
+    render's depth (sum w z) and opacity (sum w) maps, both of which carry gradients.  depth_weights [V,H,W] (>= 0) is a per-pixel
+    confidence; pixels where depths <= 0 are holes.  lambda_depth is a float or a (start, end) pair decayed exponentially over the
+    iterations (depth_weight_schedule).  `losses` then logs the total objective and the returned dict gains "depth_losses": the
+    unweighted depth term at the logged iterations.  depths=None or lambda_depth == 0 never calls depth_loss: the loop is the one above.
+    `density=` works unchanged with a depth term; its statistics see the gradient of the total objective."""
+    lambdas_depth = _check_depth_args(images, depths, depth_weights, lambda_depth, depth_mode, depth_space, depth_min_opacity, iters)
     params = tuple(params)
     for p in params:
         if p not in FIELDS:
@@ -91,7 +148,11 @@ def refine_gaussians(means, scales, rotations, opacities, harmonics, images, c2w
     cov6_of = lambda: raster.quat_scale_to_cov6(torch.roll(value("rotations"), 1, dims=-1), value("scales"))
     cov6_fixed = None if cov_moves else cov6_of()
 
+    if lambdas_depth is not None:
+        depth_target = depths.detach().float().to(dev).contiguous()
+        depth_conf = None if depth_weights is None else depth_weights.detach().float().to(dev).contiguous()
     losses: List[float] = []
+    depth_losses: List[float] = []
     events: List[dict] = []
     new_adam = lambda: torch.optim.Adam([{"params": [free[k]], "lr": lr[k]} for k in free], eps=1e-15, fused=True)
     stats, densify_at, reset_at = None, (), ()
@@ -136,16 +197,28 @@ def refine_gaussians(means, scales, rotations, opacities, harmonics, images, c2w
                             opt.state[free["opacities"]][m].zero_()
             opt.zero_grad(set_to_none=True)
             cov6 = cov6_of() if cov_moves else cov6_fixed
-            img, _ = render_cuda(c2w, Kn, near_t, far_t, (H, W), bg_t, value("means")[None].expand(V, -1, -1), cov6[None].expand(V, -1, -1),
-                                 value("harmonics")[None].expand(V, -1, -1, -1), value("opacities")[None].expand(V, -1), density_stats=stats)
-            loss = photometric_loss(img, target, lambda_dssim)
+            if lambdas_depth is None:
+                img, _ = render_cuda(c2w, Kn, near_t, far_t, (H, W), bg_t, value("means")[None].expand(V, -1, -1), cov6[None].expand(V, -1, -1),
+                                     value("harmonics")[None].expand(V, -1, -1, -1), value("opacities")[None].expand(V, -1), density_stats=stats)
+                loss = photometric_loss(img, target, lambda_dssim)
+            else:
+                img, dep, aux = render_cuda(c2w, Kn, near_t, far_t, (H, W), bg_t, value("means")[None].expand(V, -1, -1), cov6[None].expand(V, -1, -1),
+                                            value("harmonics")[None].expand(V, -1, -1, -1), value("opacities")[None].expand(V, -1), density_stats=stats,
+                                            return_aux=True)
+                opa = aux[0]["opacity"] if len(aux) == 1 else torch.cat([a["opacity"] for a in aux])
+                d_loss = depth_loss(dep, opa, depth_target, depth_conf, depth_mode, depth_space, depth_min_opacity)
+                loss = photometric_loss(img, target, lambda_dssim) + lambdas_depth[it] * d_loss
             loss.backward()
             opt.step()
             if log_every and it % int(log_every) == 0:
                 losses.append(float(loss.detach()))
+                if lambdas_depth is not None:
+                    depth_losses.append(float(d_loss.detach()))
     with torch.no_grad():
         out = {k: (value(k).detach().clone() if k in free else start[k].clone()) for k in FIELDS}
         out["covariances"] = covariances_from(out["rotations"], out["scales"])
         if density is not None:
             out["density_events"] = events
+        if lambdas_depth is not None:
+            out["depth_losses"] = depth_losses
     return out, losses
