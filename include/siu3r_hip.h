@@ -546,6 +546,36 @@ int siu3r_density_apply(int mode, const float* src, const float* m1, const float
                         const int32_t* offset, const float* quats_xyzw, const float* log_scales, const float* noise, float* dst,
                         float* dst_m1, float* dst_m2, void* stream);
 
+/* ---- fused visibility-aware Adam of splat refinement (csrc/gaussian_adam.hip): all fields in ONE launch ----
+ * A field is a dense fp32 [G, width] array on the device with its gradient and its two Adam moments, all of that shape; bases need only be
+ * 4-byte aligned (16-byte aligned bases take the 16-byte path).  The element with index i within its row steps with `lr` when
+ * head_period == 0 or i % head_period == 0 and with `lr_tail` otherwise (harmonics [G,3,n], head_period = n: DC at lr, the rest at lr_tail). */
+#define SIU3R_ADAM_MAX_FIELDS 8
+typedef struct {
+  float* param;
+  const float* grad;
+  float* exp_avg;
+  float* exp_avg_sq;
+  int32_t width;       /* floats per row, > 0 */
+  int32_t head_period; /* >= 0 */
+  float lr, lr_tail;   /* >= 0 */
+} siu3r_adam_field;
+/* fields: a HOST array of n_fields (1 .. SIU3R_ADAM_MAX_FIELDS) entries, copied into the kernel arguments (nothing is uploaded).
+ * A visible row, in fp32 and in the operation order of torch.optim.Adam (amsgrad off, no weight decay):
+ *   m = beta1 m + (1 - beta1) g;  v = beta2 v + (1 - beta2) g g;  p -= (lr / bc1) m / (sqrt(v) / sqrt(bc2) + eps)
+ * (the betas are doubles so that 1 - beta is rounded to fp32 once)
+ * with bc1 = 1 - beta1^t, bc2 = 1 - beta2^t of the caller's GLOBAL step count t (computed in double, passed as floats), also for rows that
+ * earlier calls skipped; this is this project's definition and is unverified against the sparse Adam of the 3DGS code base.  Non-finite
+ * gradients propagate, nothing is special-cased.
+ * Visibility, at most one of: radii [V,G,R] int32 (the K2 render's radii, R = 2: a row is visible iff any of its V * R entries is > 0;
+ * reduced by a small launch of its own into ws, siu3r_gaussian_adam_ws(G) BYTES on the device) or mask [G] uint8 (non-zero = visible).
+ * Both NULL: every row is visible and ws may be NULL.  An invisible row is not written (param, exp_avg, exp_avg_sq keep their bits) and its
+ * grad is not read.  Elementwise and deterministic: two calls on equal inputs give equal bits.  Nothing allocates or synchronises with the
+ * host.  Errors (a NULL pointer, width <= 0, more than 8 fields, a negative rate, both visibility forms): siu3r_last_error(). */
+int64_t siu3r_gaussian_adam_ws(int64_t G);
+int siu3r_gaussian_adam(const siu3r_adam_field* fields, int n_fields, int64_t G, double beta1, double beta2, float eps, float bc1, float bc2,
+                        const int32_t* radii, int V, int R, const uint8_t* mask, void* ws, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

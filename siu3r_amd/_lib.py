@@ -82,6 +82,14 @@ class RasterCam(C.Structure):
     ]
 
 
+class AdamField(C.Structure):
+    """siu3r_adam_field: one field of siu3r_gaussian_adam's table."""
+    _fields_ = [
+        ("param", C.c_void_p), ("grad", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p),
+        ("width", C.c_int32), ("head_period", C.c_int32), ("lr", C.c_float), ("lr_tail", C.c_float),
+    ]
+
+
 # name -> argtypes; restype is c_int unless listed in _RESTYPES.  Mirrors include/siu3r_hip.h.
 _P, _I, _L, _F = C.c_void_p, C.c_int, C.c_int64, C.c_float
 ABI_VERSION = 10  # SIU3R_ABI_VERSION of include/siu3r_hip.h these ctypes declarations mirror
@@ -149,6 +157,8 @@ SIGNATURES = {
     "siu3r_photo_loss": [_P, _P, _I, _I, _I, _I, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _F, _F, _P, _P, _P, _P],
     "siu3r_depth_loss_ws": [_I, _I, _I],
     "siu3r_depth_loss": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _P, _P, _P, _P, _P, _P, _P],
+    "siu3r_gaussian_adam_ws": [_L],
+    "siu3r_gaussian_adam": [C.POINTER(AdamField), _I, _L, C.c_double, C.c_double, _F, _F, _F, _P, _I, _I, _P, _P, _P],
     "siu3r_density_accumulate": [_P, _P, _I, _L, _F, _F, _P, _P, _P, _P],
     "siu3r_density_plan_ws": [_L],
     "siu3r_density_plan": [_P, _P, _P, _P, _P, _L, _F, _F, _F, _I, _F, _I, _P, _P, _P, _P, _P],
@@ -161,6 +171,7 @@ _RESTYPES = {"siu3r_last_error": C.c_char_p, "siu3r_raster_composite_feat_ws_byt
 _RESTYPES["siu3r_photo_loss_partials"] = C.c_int64
 _RESTYPES["siu3r_density_plan_ws"] = C.c_int64
 _RESTYPES["siu3r_depth_loss_ws"] = C.c_int64
+_RESTYPES["siu3r_gaussian_adam_ws"] = C.c_int64
 
 _lib = None
 

@@ -1,7 +1,8 @@
 """Per-scene refinement: optimise the Gaussians themselves against posed target images (the second inference-time use of the HIP rasterizer
 backward; the first is pose_align.align_pose).  Every iteration is ONE multi-view K2 render (cuda_splatting.render_cuda), ONE fused photometric
-loss (losses.photometric_loss) and one backward; the optimiser is torch's Adam.  A caller whose views are unposed aligns them first
-(align_pose) and refines second."""
+loss (losses.photometric_loss) and one backward; the optimiser is torch's Adam or, with optimizer="hip", the fused visibility-aware Adam of
+optim.GaussianAdam (one HIP launch per iteration for all fields).  A caller whose views are unposed aligns them first (align_pose) and
+refines second."""
 from __future__ import annotations
 
 import math
@@ -13,10 +14,12 @@ from . import raster
 from .cuda_splatting import render_cuda
 from .density import DensityControl, DensityStats, densify_and_prune, scene_extent
 from .losses import DEPTH_MODES, DEPTH_SPACES, depth_loss, photometric_loss
+from .optim import GaussianAdam, means_lr_schedule
 
 FIELDS = ("means", "scales", "rotations", "opacities", "harmonics")
-# Adam steps per field, those of the 3DGS training recipe (Kerbl et al. 2023): position 1.6e-4 (there times the scene extent, and decayed),
-# scaling 5e-3, rotation 1e-3, opacity 5e-2, SH 2.5e-3 (there the higher bands at a twentieth)
+# Adam steps per field, those of the 3DGS training recipe (Kerbl et al. 2023): position 1.6e-4, scaling 5e-3, rotation 1e-3, opacity 5e-2,
+# SH 2.5e-3.  The recipe also multiplies the position rate by the scene extent and decays it, and steps the higher SH bands at a twentieth:
+# refine_gaussians does so with optimizer="hip" (means_lr_extent_scale, means_lr_final, sh_rest_lr_scale); the default torch path does not.
 DEFAULT_LRS = {"means": 1.6e-4, "scales": 5e-3, "rotations": 1e-3, "opacities": 5e-2, "harmonics": 2.5e-3}
 _COV33 = (0, 1, 2, 1, 3, 4, 2, 4, 5)  # [G,6] upper triangle -> [G,3,3]
 
@@ -74,10 +77,31 @@ def _check_depth_args(images, depths, depth_weights, lambda_depth, depth_mode, d
     return None if off else schedule
 
 
+OPTIMIZERS = ("torch", "hip")
+
+
+def _check_optim_args(optimizer, sparse, means_lr_final, means_lr_extent_scale, sh_rest_lr_scale) -> bool:
+    """host-side validation of refine_gaussians' optimiser keywords, before any device work; True for the HIP optimiser"""
+    if optimizer not in OPTIMIZERS:
+        raise ValueError(f"optimizer must be one of {OPTIMIZERS}, got {optimizer!r}")
+    if means_lr_final is not None and not 0.0 < float(means_lr_final) < math.inf:
+        raise ValueError(f"means_lr_final must be positive and finite (or None), got {means_lr_final!r}")
+    if not 0.0 <= float(sh_rest_lr_scale) < math.inf:
+        raise ValueError(f"sh_rest_lr_scale must be finite and >= 0, got {sh_rest_lr_scale!r}")
+    if optimizer == "torch":
+        asked = [name for name, on in (("sparse", bool(sparse)), ("means_lr_final", means_lr_final is not None),
+                                       ("means_lr_extent_scale", bool(means_lr_extent_scale)), ("sh_rest_lr_scale", float(sh_rest_lr_scale) != 1.0)) if on]
+        if asked:
+            raise ValueError(f'{", ".join(asked)}: only optimizer="hip" implements this (optimizer="torch" is plain torch.optim.Adam)')
+    return optimizer == "hip"
+
+
 def refine_gaussians(means, scales, rotations, opacities, harmonics, images, c2w, Kn, near, far, bg, iters: int = 200, lambda_dssim: float = 0.2,
                      lrs: Optional[Dict[str, float]] = None, params: Sequence[str] = FIELDS, log_every: int = 1,
                      density: Optional[DensityControl] = None, depths=None, depth_weights=None, lambda_depth=0.0, depth_mode: str = "l1",
-                     depth_space: str = "depth", depth_min_opacity: float = 0.5) -> Tuple[Dict[str, torch.Tensor], List[float]]:
+                     depth_space: str = "depth", depth_min_opacity: float = 0.5, optimizer: str = "torch", sparse: bool = False,
+                     means_lr_final: Optional[float] = None, means_lr_extent_scale: bool = False,
+                     sh_rest_lr_scale: float = 1.0) -> Tuple[Dict[str, torch.Tensor], List[float]]:
     """means [G,3], scales [G,3], rotations [G,4], opacities [G], harmonics [G,3,n] (n = (deg+1)^2): what `Gaussians` carries, on the GPU.
     images [V,3,H,W]: the posed target views; c2w [V,4,4] camera-to-world, Kn [V,3,3] (or [3,3]) normalised intrinsics, near / far floats
     (or [V]), bg 3 floats: render_cuda's conventions.
@@ -113,8 +137,18 @@ def refine_gaussians(means, scales, rotations, opacities, harmonics, images, c2w
     confidence; pixels where depths <= 0 are holes.  lambda_depth is a float or a (start, end) pair decayed exponentially over the
     iterations (depth_weight_schedule).  `losses` then logs the total objective and the returned dict gains "depth_losses": the
     unweighted depth term at the logged iterations.  depths=None or lambda_depth == 0 never calls depth_loss: the loop is the one above.
-    `density=` works unchanged with a depth term; its statistics see the gradient of the total objective."""
+    `density=` works unchanged with a depth term; its statistics see the gradient of the total objective.
+
+    optimizer: "torch" (the default: the loop above, bit for bit) or "hip": optim.GaussianAdam, one fused launch per iteration for all free
+    fields with the same arithmetic per element.  Only "hip" takes the remaining keywords (with "torch" they raise ValueError):
+    sparse=True asks every iteration's render for its radii and skips the Gaussians no training view saw (parameters and moments keep their
+    bits; the bias correction still uses the global step count);  means_lr_final decays the `means` rate log-linearly from its `lrs` value
+    to this over `iters` (optim.means_lr_schedule);  means_lr_extent_scale=True multiplies both ends by the scene extent
+    (density.scene_extent of the control when it names one, else density.scene_extent(c2w): one host read);  sh_rest_lr_scale steps the SH
+    coefficients above DC at that fraction of the `harmonics` rate (3DGS: 0.05).  `density=` and the depth keywords work as above; the
+    returned dict gains "optimizer_steps", the optimiser's step count (== iters, also across density events)."""
     lambdas_depth = _check_depth_args(images, depths, depth_weights, lambda_depth, depth_mode, depth_space, depth_min_opacity, iters)
+    hip = _check_optim_args(optimizer, sparse, means_lr_final, means_lr_extent_scale, sh_rest_lr_scale)
     params = tuple(params)
     for p in params:
         if p not in FIELDS:
@@ -163,41 +197,65 @@ def refine_gaussians(means, scales, rotations, opacities, harmonics, images, c2w
         stats = DensityStats(means.shape[0], dev)
         noise_gen = torch.Generator(device=dev).manual_seed(int(density.seed))
         unconstrained = {}  # the frozen fields in the form the density kernels read, made at the first event
+    means_lrs = None  # the `means` rate per iteration, where it is not the constant lr["means"]
+    if hip and "means" in free and (means_lr_final is not None or means_lr_extent_scale):
+        lr_scale = 1.0
+        if means_lr_extent_scale:
+            lr_scale = float(density.scene_extent) if density is not None and density.scene_extent is not None else scene_extent(c2w)
+        means_lrs = means_lr_schedule(lr["means"] * lr_scale, (lr["means"] if means_lr_final is None else float(means_lr_final)) * lr_scale, int(iters))
     if free:
-        opt = new_adam()
+        opt = GaussianAdam(free, {k: lr[k] for k in free}, eps=1e-15, sh_rest_lr_scale=float(sh_rest_lr_scale)) if hip else new_adam()
         for it in range(int(iters)):
             if it in densify_at:
                 for k in FIELDS:
                     if k not in free and k not in unconstrained:
                         unconstrained[k] = to_param[k](start[k])
-                state = {k: opt.state[free[k]] for k in free}
+                if hip:
+                    moments = opt.moments
+                else:
+                    state = {k: opt.state[free[k]] for k in free}
+                    moments = {k: (state[k]["exp_avg"], state[k]["exp_avg_sq"]) for k in free}
                 noise = torch.randn((stats.G, 2, 3), generator=noise_gen, device=dev, dtype=torch.float32)
-                new_p, new_m, info = densify_and_prune({k: (free[k].detach() if k in free else unconstrained[k]) for k in FIELDS},
-                                                       {k: (state[k]["exp_avg"], state[k]["exp_avg_sq"]) for k in free}, stats, density, extent, noise)
+                new_p, new_m, info = densify_and_prune({k: (free[k].detach() if k in free else unconstrained[k]) for k in FIELDS}, moments, stats, density,
+                                                       extent, noise)
                 if info["rows_out"] == 0:
                     raise RuntimeError(f"density control pruned every Gaussian at iteration {it}: {info}")
                 events.append(dict(info, iteration=it))
-                steps = {k: state[k]["step"] for k in free}  # (fused Adam: a device tensor per parameter)
+                if not hip:
+                    steps = {k: state[k]["step"] for k in free}  # (fused Adam: a device tensor per parameter)
                 free = {k: new_p[k].requires_grad_(True) for k in free}
                 for k in FIELDS:
                     if k not in free:
                         unconstrained[k] = new_p[k]
                         start[k] = from_param[k](new_p[k])
-                opt = new_adam()
-                for k in free:
-                    opt.state[free[k]] = {"step": steps[k], "exp_avg": new_m[k][0], "exp_avg_sq": new_m[k][1]}
+                if hip:
+                    opt.rebind(free, new_m)  # (the step count stays)
+                else:
+                    opt = new_adam()
+                    for k in free:
+                        opt.state[free[k]] = {"step": steps[k], "exp_avg": new_m[k][0], "exp_avg_sq": new_m[k][1]}
                 cov6_fixed = None if cov_moves else cov6_of()
                 stats = DensityStats(info["rows_out"], dev)
             if it in reset_at and "opacities" in free:
                 with torch.no_grad():
                     p = float(density.reset_opacity)
                     free["opacities"].clamp_(max=math.log(p / (1.0 - p)))
-                    for m in ("exp_avg", "exp_avg_sq"):
-                        if m in opt.state[free["opacities"]]:
-                            opt.state[free["opacities"]][m].zero_()
+                    if hip:
+                        opt.zero_moments("opacities")
+                    else:
+                        for m in ("exp_avg", "exp_avg_sq"):
+                            if m in opt.state[free["opacities"]]:
+                                opt.state[free["opacities"]][m].zero_()
             opt.zero_grad(set_to_none=True)
             cov6 = cov6_of() if cov_moves else cov6_fixed
-            if lambdas_depth is None:
+            radii = None
+            if lambdas_depth is None and sparse:
+                img, _, aux = render_cuda(c2w, Kn, near_t, far_t, (H, W), bg_t, value("means")[None].expand(V, -1, -1), cov6[None].expand(V, -1, -1),
+                                          value("harmonics")[None].expand(V, -1, -1, -1), value("opacities")[None].expand(V, -1), density_stats=stats,
+                                          return_aux=True)
+                radii = aux[0]["radii"] if len(aux) == 1 else torch.cat([a["radii"] for a in aux])
+                loss = photometric_loss(img, target, lambda_dssim)
+            elif lambdas_depth is None:
                 img, _ = render_cuda(c2w, Kn, near_t, far_t, (H, W), bg_t, value("means")[None].expand(V, -1, -1), cov6[None].expand(V, -1, -1),
                                      value("harmonics")[None].expand(V, -1, -1, -1), value("opacities")[None].expand(V, -1), density_stats=stats)
                 loss = photometric_loss(img, target, lambda_dssim)
@@ -206,10 +264,15 @@ def refine_gaussians(means, scales, rotations, opacities, harmonics, images, c2w
                                             value("harmonics")[None].expand(V, -1, -1, -1), value("opacities")[None].expand(V, -1), density_stats=stats,
                                             return_aux=True)
                 opa = aux[0]["opacity"] if len(aux) == 1 else torch.cat([a["opacity"] for a in aux])
+                if sparse:
+                    radii = aux[0]["radii"] if len(aux) == 1 else torch.cat([a["radii"] for a in aux])
                 d_loss = depth_loss(dep, opa, depth_target, depth_conf, depth_mode, depth_space, depth_min_opacity)
                 loss = photometric_loss(img, target, lambda_dssim) + lambdas_depth[it] * d_loss
             loss.backward()
-            opt.step()
+            if hip:
+                opt.step(visible=radii, lrs=None if means_lrs is None else {"means": means_lrs[it]})
+            else:
+                opt.step()
             if log_every and it % int(log_every) == 0:
                 losses.append(float(loss.detach()))
                 if lambdas_depth is not None:
@@ -221,4 +284,6 @@ def refine_gaussians(means, scales, rotations, opacities, harmonics, images, c2w
             out["density_events"] = events
         if lambdas_depth is not None:
             out["depth_losses"] = depth_losses
+        if hip:
+            out["optimizer_steps"] = opt.step_count if free else 0
     return out, losses
