@@ -14,7 +14,7 @@
 // Work split: a workgroup (256 threads, 4 pixels each, 16-byte accesses where the plane's base allows) owns 1,024 pixels of ONE view; it
 // reduces by a fixed shuffle tree per wave, then the four waves in index order, and writes one record of REC doubles.  One workgroup then
 // adds the records of each view in a fixed order (chunks of 256).  No atomics: two calls give the same bits.
-#include "common.h"
+#include "block_reduce.h"
 
 namespace {
 
@@ -37,8 +37,6 @@ struct DepthArgs {
   int P, bpv, inverse;
   float min_opacity;
 };
-
-__device__ inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 // PX consecutive values of one plane; `fill` past the end of the plane
 __device__ inline void load_px(const float* plane, int i0, int P, bool vec, float fill, float (&v)[PX]) {
@@ -107,30 +105,6 @@ __device__ inline void load_pixels(const DepthArgs& a, Pixels& p) {
   }
 }
 
-// fixed-order reductions over the workgroup: shuffle tree per wave, then the four waves in index order.  OP 0 sum, 1 min, 2 max.
-template <int OP>
-__device__ inline double combine(double a, double b) {
-  return OP == 0 ? a + b : (OP == 1 ? fmin(a, b) : fmax(a, b));
-}
-
-template <int OP, int K>
-__device__ inline void block_reduce(double (&v)[K], double* red /* [K][4] */) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int k = 0; k < K; ++k) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v[k] = combine<OP>(v[k], __shfl_down(v[k], o, 64));
-  }
-  __syncthreads();  // (the previous use of `red` is over)
-  if (lane == 0) {
-#pragma unroll
-    for (int k = 0; k < K; ++k) red[4 * k + wave] = v[k];
-  }
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < K; ++k) v[k] = combine<OP>(combine<OP>(combine<OP>(red[4 * k], red[4 * k + 1]), red[4 * k + 2]), red[4 * k + 3]);
-}
-
 // mode l1: sums and, with GRAD, the gradient without its 1 / N
 template <bool GRAD>
 __global__ __launch_bounds__(NT) void depth_l1_kernel(DepthArgs a) {
@@ -158,7 +132,7 @@ __global__ __launch_bounds__(NT) void depth_l1_kernel(DepthArgs a) {
     store_px(a.g_depth + p.base, p.i0, a.P, p.vec, gd);
     store_px(a.g_opacity + p.base, p.i0, a.P, p.vec, go);
   }
-  block_reduce<0>(s, red);
+  block_reduce<Reduce::Sum>(s, red);
   if (threadIdx.x == 0) {
     double* r = a.partials + ((int64_t)blockIdx.y * a.bpv + blockIdx.x) * REC;
     r[0] = s[0], r[1] = s[1], r[2] = s[2];
@@ -187,9 +161,9 @@ __global__ __launch_bounds__(NT) void depth_moments_kernel(DepthArgs a) {
       lo[1] = fmin(lo[1], y), hi[1] = fmax(hi[1], y);
     }
   }
-  block_reduce<0>(s, red);
-  block_reduce<1>(lo, red);
-  block_reduce<2>(hi, red);
+  block_reduce<Reduce::Sum>(s, red);
+  block_reduce<Reduce::Min>(lo, red);
+  block_reduce<Reduce::Max>(hi, red);
   if (threadIdx.x == 0) {
     double* r = a.partials + ((int64_t)blockIdx.y * a.bpv + blockIdx.x) * REC;
 #pragma unroll
@@ -240,10 +214,10 @@ __global__ __launch_bounds__(NT) void depth_finalize_kernel(const double* partia
         lo[1] = fmin(lo[1], r[9]), hi[1] = fmax(hi[1], r[10]);
       }
     }
-    block_reduce<0>(s, red);
+    block_reduce<Reduce::Sum>(s, red);
     if (pearson) {
-      block_reduce<1>(lo, red);
-      block_reduce<2>(hi, red);
+      block_reduce<Reduce::Min>(lo, red);
+      block_reduce<Reduce::Max>(hi, red);
     }
     // every thread holds the same totals; thread 0 writes
     if (!pearson) {

@@ -18,7 +18,7 @@
 // accesses where the four bases of the field allow and the four elements are all visible, scalar accesses otherwise) takes chunks in a
 // grid-stride loop over at most 2,048 workgroups.  Elementwise, no atomics: two calls on equal inputs give equal bits.  All element and
 // row indices are 64-bit.
-#include "common.h"
+#include "block_reduce.h"
 
 namespace {
 
@@ -36,8 +36,6 @@ struct AdamArgs {
   int n_fields;
   float b1, omb1, b2, omb2, eps, bc1, bc2;
 };
-
-__device__ inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 
 __device__ inline void adam1(float& p, float g, float& m, float& v, float step, float b1, float omb1, float b2, float omb2, float bc2s, float eps) {
   m = b1 * m + omb1 * g;

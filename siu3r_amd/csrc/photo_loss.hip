@@ -12,7 +12,7 @@
 // With p' = p - cp, t' = t - ct the centred form  dSSIM/dp(x) = sum_w g(w, x) [ dmu_c + 2 d_epp (p(x) - mu_p(w)) + d_ept (t(x) - mu_t(w)) ]
 // needs only shifted quantities: d_mu' = dmu_c - 2 d_epp mu_p' - d_ept mu_t', dmu_c = 2 mu_t A2 / (B1 B2) - 2 mu_p A1 A2 / (B1^2 B2).
 // The value is deterministic: per-workgroup partial sums (fixed tree) into `partials`, then one workgroup adds them in a fixed order.
-#include "common.h"
+#include "block_reduce.h"
 
 namespace {
 
@@ -38,15 +38,11 @@ struct PhotoArgs {
   int do_l1;
 };
 
-// fixed-order sum over the workgroup: xor-free shuffle tree per wave, then the four wave sums in index order
+// fixed-order sum over the workgroup (block_reduce.h): shuffle tree per wave, then the four wave sums in index order
 __device__ inline float block_sum(float v, float* red) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_down(v, o, 64);
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  __syncthreads();
-  if (lane == 0) red[wave] = v;
-  __syncthreads();
-  return red[0] + red[1] + red[2] + red[3];
+  float s[1] = {v};
+  block_reduce<Reduce::Sum>(s, red);
+  return s[0];
 }
 
 // GRAD: windows [tile - 10, tile + 32) and pixels [tile - 10, tile + 42); otherwise windows [tile, tile + 32), pixels [tile, tile + 42)

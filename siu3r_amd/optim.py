@@ -3,7 +3,10 @@ DESIGN.md section 12), which leaves alone the Gaussians that no view of the iter
 3DGS training recipe (Kerbl et al. 2023): the higher SH bands at a fraction of the DC rate, a log-linear decay of the position rate.
 
 The arithmetic of a visible row is torch.optim.Adam's (amsgrad off, no weight decay) in float32; the bias corrections use the optimiser's
-GLOBAL step count, also for a row that earlier steps skipped.  There is no CPU path and nothing here synchronises with the host."""
+GLOBAL step count, also for a row that earlier steps skipped.  There is no CPU path and nothing here synchronises with the host.
+
+TorchAdam puts torch.optim.Adam behind the same surface (moments / rebind / zero_moments / zero_grad / step), so that refine.refine_gaussians
+drives either optimiser with one set of statements."""
 from __future__ import annotations
 
 import math
@@ -19,6 +22,13 @@ MAX_FIELDS = 8  # SIU3R_ADAM_MAX_FIELDS
 SH_FIELD = "harmonics"  # [G,3,n]: the field whose first coefficient per colour steps at lr and the others at lr * sh_rest_lr_scale
 
 
+def log_linear(a: float, b: float, n: int) -> List[float]:
+    """n values from a to b (both positive), v_t = a * (b / a) ** (t / (n - 1)) with both endpoints exact; n <= 1 gives [a] * n"""
+    if n <= 1:
+        return [a] * n
+    return [a] + [a * (b / a) ** (t / (n - 1)) for t in range(1, n - 1)] + [b]
+
+
 def means_lr_schedule(lr_init: float, lr_final: float, iters: int) -> List[float]:
     """The position learning rate at every iteration: log-linear interpolation lr_t = lr_init * (lr_final / lr_init) ** (t / (iters - 1))
     with both endpoints exact (the decay of the 3DGS recipe, without its delay); iters == 1 gives [lr_init]."""
@@ -26,9 +36,7 @@ def means_lr_schedule(lr_init: float, lr_final: float, iters: int) -> List[float
     a, b = float(lr_init), float(lr_final)
     if not (0.0 < a < math.inf and 0.0 < b < math.inf):
         raise ValueError(f"means_lr_schedule: lr_init and lr_final must both be positive and finite, got {lr_init!r}, {lr_final!r}")
-    if n <= 1:
-        return [a] * n
-    return [a] + [a * (b / a) ** (t / (n - 1)) for t in range(1, n - 1)] + [b]
+    return log_linear(a, b, n)
 
 
 def _rate(name: str, v) -> float:
@@ -179,3 +187,44 @@ class GaussianAdam:
             check(lib.siu3r_gaussian_adam(table, len(self.params), self.G, b1, b2, self.eps, 1.0 - b1 ** t, 1.0 - b2 ** t, _p(radii), V, R, _p(mask),
                                           _p(self._ws) if radii is not None else None, _stream()))
         self.step_count = t
+
+
+class TorchAdam:
+    """torch.optim.Adam (fused, one parameter group per field) behind the part of GaussianAdam's surface that refine.refine_gaussians uses, so
+    that the loop never sees torch's optimiser-state format.  It steps every row at its constant rate: no visibility, no schedule."""
+
+    def __init__(self, params: Dict[str, torch.Tensor], lrs: Dict[str, float], eps: float = 1e-15):
+        self.lrs, self.eps = {k: lrs[k] for k in params}, eps
+        self._bind(params)
+
+    def _bind(self, params):
+        self.params = dict(params)
+        self._opt = torch.optim.Adam([{"params": [p], "lr": self.lrs[k]} for k, p in self.params.items()], eps=self.eps, fused=True)
+
+    @property
+    def moments(self) -> Dict[str, Tuple[torch.Tensor, torch.Tensor]]:
+        """{field: (exp_avg, exp_avg_sq)} of the optimiser's state (there from the first step on)"""
+        state = {k: self._opt.state[p] for k, p in self.params.items()}
+        return {k: (state[k]["exp_avg"], state[k]["exp_avg_sq"]) for k in state}
+
+    def rebind(self, params: Dict[str, torch.Tensor], moments: Dict[str, Tuple[torch.Tensor, torch.Tensor]]):
+        """a new torch.optim.Adam on the new leaves after a density event, with each field's step count (fused Adam: a device tensor per
+        parameter) and the given moments as its state"""
+        steps = {k: self._opt.state[p]["step"] for k, p in self.params.items()}
+        self._bind({k: params[k] for k in self.params})
+        for k, p in self.params.items():
+            self._opt.state[p] = {"step": steps[k], "exp_avg": moments[k][0], "exp_avg_sq": moments[k][1]}
+
+    def zero_moments(self, field: str):
+        state = self._opt.state[self.params[field]]
+        for m in ("exp_avg", "exp_avg_sq"):
+            if m in state:  # (before the first step there is nothing to zero)
+                state[m].zero_()
+
+    def zero_grad(self, set_to_none: bool = True):
+        self._opt.zero_grad(set_to_none=set_to_none)
+
+    def step(self, visible=None, lrs=None):
+        if visible is not None or lrs is not None:
+            raise ValueError("TorchAdam.step takes neither `visible` nor `lrs`: only GaussianAdam implements them")
+        self._opt.step()

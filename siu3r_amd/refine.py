@@ -12,16 +12,19 @@ import torch
 
 from . import raster
 from .cuda_splatting import render_cuda
-from .density import DensityControl, DensityStats, densify_and_prune, scene_extent
+from .density import FIELDS, DensityControl, DensityStats, densify_and_prune, scene_extent
 from .losses import DEPTH_MODES, DEPTH_SPACES, depth_loss, photometric_loss
-from .optim import GaussianAdam, means_lr_schedule
+from .optim import GaussianAdam, TorchAdam, log_linear, means_lr_schedule
 
-FIELDS = ("means", "scales", "rotations", "opacities", "harmonics")
 # Adam steps per field, those of the 3DGS training recipe (Kerbl et al. 2023): position 1.6e-4, scaling 5e-3, rotation 1e-3, opacity 5e-2,
 # SH 2.5e-3.  The recipe also multiplies the position rate by the scene extent and decays it, and steps the higher SH bands at a twentieth:
 # refine_gaussians does so with optimizer="hip" (means_lr_extent_scale, means_lr_final, sh_rest_lr_scale); the default torch path does not.
 DEFAULT_LRS = {"means": 1.6e-4, "scales": 5e-3, "rotations": 1e-3, "opacities": 5e-2, "harmonics": 2.5e-3}
 _COV33 = (0, 1, 2, 1, 3, 4, 2, 4, 5)  # [G,6] upper triangle -> [G,3,3]
+# a field <-> the unconstrained form that is optimised (and that the density kernels read)
+_TO_PARAM = {"means": lambda x: x.clone(), "scales": torch.log, "rotations": lambda x: x.clone(),
+             "opacities": lambda x: torch.logit(x.clamp(1e-6, 1 - 1e-6)), "harmonics": lambda x: x.clone()}
+_FROM_PARAM = {"means": lambda x: x, "scales": torch.exp, "rotations": lambda x: x, "opacities": torch.sigmoid, "harmonics": lambda x: x}
 
 
 def covariances_from(rotations_xyzw: torch.Tensor, scales: torch.Tensor) -> torch.Tensor:
@@ -41,9 +44,7 @@ def depth_weight_schedule(lambda_depth, iters: int) -> List[float]:
         a, b = float(lambda_depth[0]), float(lambda_depth[1])
         if not (0.0 < a < math.inf and 0.0 < b < math.inf):
             raise ValueError(f"lambda_depth (start, end) must both be positive and finite, got {lambda_depth!r}")
-        if n <= 1:
-            return [a] * n
-        return [a] + [a * (b / a) ** (t / (n - 1)) for t in range(1, n - 1)] + [b]
+        return log_linear(a, b, n)
     lam = float(lambda_depth)
     if not math.isfinite(lam):
         raise ValueError(f"lambda_depth must be finite, got {lambda_depth!r}")
@@ -78,6 +79,11 @@ def _check_depth_args(images, depths, depth_weights, lambda_depth, depth_mode, d
 
 
 OPTIMIZERS = ("torch", "hip")
+
+
+def _aux_cat(aux: List[dict], key: str) -> torch.Tensor:
+    """one field of render_cuda's aux (a dict per view group) over all views"""
+    return aux[0][key] if len(aux) == 1 else torch.cat([a[key] for a in aux])
 
 
 def _check_optim_args(optimizer, sparse, means_lr_final, means_lr_extent_scale, sh_rest_lr_scale) -> bool:
@@ -172,113 +178,92 @@ def refine_gaussians(means, scales, rotations, opacities, harmonics, images, c2w
     near_t, far_t = as_v(near), as_v(far)
     bg_t = torch.tensor([[float(b) for b in bg]]).expand(V, 3)
 
-    # the free fields in their unconstrained form
-    to_param = {"means": lambda x: x.clone(), "scales": torch.log, "rotations": lambda x: x.clone(),
-                "opacities": lambda x: torch.logit(x.clamp(1e-6, 1 - 1e-6)), "harmonics": lambda x: x.clone()}
-    from_param = {"means": lambda x: x, "scales": torch.exp, "rotations": lambda x: x, "opacities": torch.sigmoid, "harmonics": lambda x: x}
-    free = {k: to_param[k](start[k]).requires_grad_(True) for k in FIELDS if k in params}
-    value = lambda k: from_param[k](free[k]) if k in free else start[k]
+    # the free fields in their unconstrained form; `value` and `cov6_of` read a field through whichever leaves they are handed
+    free = {k: _TO_PARAM[k](start[k]).requires_grad_(True) for k in FIELDS if k in params}
+    value = lambda k, leaves: _FROM_PARAM[k](leaves[k]) if k in leaves else start[k]
     cov_moves = "scales" in free or "rotations" in free
-    cov6_of = lambda: raster.quat_scale_to_cov6(torch.roll(value("rotations"), 1, dims=-1), value("scales"))
-    cov6_fixed = None if cov_moves else cov6_of()
+    cov6_of = lambda leaves: raster.quat_scale_to_cov6(torch.roll(value("rotations", leaves), 1, dims=-1), value("scales", leaves))
+    cov6_fixed = None if cov_moves else cov6_of(free)
 
     if lambdas_depth is not None:
         depth_target = depths.detach().float().to(dev).contiguous()
         depth_conf = None if depth_weights is None else depth_weights.detach().float().to(dev).contiguous()
+    want_aux = lambdas_depth is not None or bool(sparse)  # (it selects want_n_touched: off for the plain path)
     losses: List[float] = []
     depth_losses: List[float] = []
     events: List[dict] = []
-    new_adam = lambda: torch.optim.Adam([{"params": [free[k]], "lr": lr[k]} for k in free], eps=1e-15, fused=True)
+    extent = None  # of the scene: one host read unless the control names it
+    if (density is not None and free) or (means_lr_extent_scale and "means" in free):
+        extent = float(density.scene_extent) if density is not None and density.scene_extent is not None else scene_extent(c2w)
     stats, densify_at, reset_at = None, (), ()
     if density is not None and free:
-        extent = float(density.scene_extent) if density.scene_extent is not None else scene_extent(c2w)
         density.thresholds(extent)  # (a bad extent raises here, not at the first event)
         densify_at, reset_at = density.events(int(iters))
         stats = DensityStats(means.shape[0], dev)
         noise_gen = torch.Generator(device=dev).manual_seed(int(density.seed))
         unconstrained = {}  # the frozen fields in the form the density kernels read, made at the first event
-    means_lrs = None  # the `means` rate per iteration, where it is not the constant lr["means"]
-    if hip and "means" in free and (means_lr_final is not None or means_lr_extent_scale):
-        lr_scale = 1.0
-        if means_lr_extent_scale:
-            lr_scale = float(density.scene_extent) if density is not None and density.scene_extent is not None else scene_extent(c2w)
+    means_lrs = None  # the `means` rate per iteration, where it is not the constant lr["means"] (optimizer="hip" only: _check_optim_args)
+    if "means" in free and (means_lr_final is not None or means_lr_extent_scale):
+        lr_scale = extent if means_lr_extent_scale else 1.0
         means_lrs = means_lr_schedule(lr["means"] * lr_scale, (lr["means"] if means_lr_final is None else float(means_lr_final)) * lr_scale, int(iters))
+    opt = None
     if free:
-        opt = GaussianAdam(free, {k: lr[k] for k in free}, eps=1e-15, sh_rest_lr_scale=float(sh_rest_lr_scale)) if hip else new_adam()
-        for it in range(int(iters)):
-            if it in densify_at:
-                for k in FIELDS:
-                    if k not in free and k not in unconstrained:
-                        unconstrained[k] = to_param[k](start[k])
-                if hip:
-                    moments = opt.moments
-                else:
-                    state = {k: opt.state[free[k]] for k in free}
-                    moments = {k: (state[k]["exp_avg"], state[k]["exp_avg_sq"]) for k in free}
-                noise = torch.randn((stats.G, 2, 3), generator=noise_gen, device=dev, dtype=torch.float32)
-                new_p, new_m, info = densify_and_prune({k: (free[k].detach() if k in free else unconstrained[k]) for k in FIELDS}, moments, stats, density,
-                                                       extent, noise)
-                if info["rows_out"] == 0:
-                    raise RuntimeError(f"density control pruned every Gaussian at iteration {it}: {info}")
-                events.append(dict(info, iteration=it))
-                if not hip:
-                    steps = {k: state[k]["step"] for k in free}  # (fused Adam: a device tensor per parameter)
-                free = {k: new_p[k].requires_grad_(True) for k in free}
-                for k in FIELDS:
-                    if k not in free:
-                        unconstrained[k] = new_p[k]
-                        start[k] = from_param[k](new_p[k])
-                if hip:
-                    opt.rebind(free, new_m)  # (the step count stays)
-                else:
-                    opt = new_adam()
-                    for k in free:
-                        opt.state[free[k]] = {"step": steps[k], "exp_avg": new_m[k][0], "exp_avg_sq": new_m[k][1]}
-                cov6_fixed = None if cov_moves else cov6_of()
-                stats = DensityStats(info["rows_out"], dev)
-            if it in reset_at and "opacities" in free:
-                with torch.no_grad():
-                    p = float(density.reset_opacity)
-                    free["opacities"].clamp_(max=math.log(p / (1.0 - p)))
-                    if hip:
-                        opt.zero_moments("opacities")
-                    else:
-                        for m in ("exp_avg", "exp_avg_sq"):
-                            if m in opt.state[free["opacities"]]:
-                                opt.state[free["opacities"]][m].zero_()
-            opt.zero_grad(set_to_none=True)
-            cov6 = cov6_of() if cov_moves else cov6_fixed
-            radii = None
-            if lambdas_depth is None and sparse:
-                img, _, aux = render_cuda(c2w, Kn, near_t, far_t, (H, W), bg_t, value("means")[None].expand(V, -1, -1), cov6[None].expand(V, -1, -1),
-                                          value("harmonics")[None].expand(V, -1, -1, -1), value("opacities")[None].expand(V, -1), density_stats=stats,
-                                          return_aux=True)
-                radii = aux[0]["radii"] if len(aux) == 1 else torch.cat([a["radii"] for a in aux])
-                loss = photometric_loss(img, target, lambda_dssim)
-            elif lambdas_depth is None:
-                img, _ = render_cuda(c2w, Kn, near_t, far_t, (H, W), bg_t, value("means")[None].expand(V, -1, -1), cov6[None].expand(V, -1, -1),
-                                     value("harmonics")[None].expand(V, -1, -1, -1), value("opacities")[None].expand(V, -1), density_stats=stats)
-                loss = photometric_loss(img, target, lambda_dssim)
-            else:
-                img, dep, aux = render_cuda(c2w, Kn, near_t, far_t, (H, W), bg_t, value("means")[None].expand(V, -1, -1), cov6[None].expand(V, -1, -1),
-                                            value("harmonics")[None].expand(V, -1, -1, -1), value("opacities")[None].expand(V, -1), density_stats=stats,
-                                            return_aux=True)
-                opa = aux[0]["opacity"] if len(aux) == 1 else torch.cat([a["opacity"] for a in aux])
-                if sparse:
-                    radii = aux[0]["radii"] if len(aux) == 1 else torch.cat([a["radii"] for a in aux])
-                d_loss = depth_loss(dep, opa, depth_target, depth_conf, depth_mode, depth_space, depth_min_opacity)
-                loss = photometric_loss(img, target, lambda_dssim) + lambdas_depth[it] * d_loss
-            loss.backward()
-            if hip:
-                opt.step(visible=radii, lrs=None if means_lrs is None else {"means": means_lrs[it]})
-            else:
-                opt.step()
-            if log_every and it % int(log_every) == 0:
-                losses.append(float(loss.detach()))
-                if lambdas_depth is not None:
-                    depth_losses.append(float(d_loss.detach()))
+        free_lrs = {k: lr[k] for k in free}
+        opt = GaussianAdam(free, free_lrs, eps=1e-15, sh_rest_lr_scale=float(sh_rest_lr_scale)) if hip else TorchAdam(free, free_lrs, eps=1e-15)
+
+    def density_event(it: int) -> Dict[str, torch.Tensor]:
+        """clone / split / prune before iteration `it`'s render: every field and the free ones' moments go through densify_and_prune, the
+        optimiser moves to the new leaves (its step count stays), the frozen fields and the statistics follow; returns the new leaves"""
+        nonlocal stats, cov6_fixed
+        for k in FIELDS:
+            if k not in free and k not in unconstrained:
+                unconstrained[k] = _TO_PARAM[k](start[k])
+        moments = opt.moments
+        noise = torch.randn((stats.G, 2, 3), generator=noise_gen, device=dev, dtype=torch.float32)
+        new_p, new_m, info = densify_and_prune({k: (free[k].detach() if k in free else unconstrained[k]) for k in FIELDS}, moments, stats, density,
+                                               extent, noise)
+        if info["rows_out"] == 0:
+            raise RuntimeError(f"density control pruned every Gaussian at iteration {it}: {info}")
+        events.append(dict(info, iteration=it))
+        leaves = {k: new_p[k].requires_grad_(True) for k in free}
+        for k in FIELDS:
+            if k not in leaves:
+                unconstrained[k] = new_p[k]
+                start[k] = _FROM_PARAM[k](new_p[k])
+        opt.rebind(leaves, new_m)
+        cov6_fixed = None if cov_moves else cov6_of(leaves)
+        stats = DensityStats(info["rows_out"], dev)
+        return leaves
+
+    for it in range(int(iters) if free else 0):
+        if it in densify_at:
+            free = density_event(it)
+        if it in reset_at and "opacities" in free:
+            with torch.no_grad():
+                p = float(density.reset_opacity)
+                free["opacities"].clamp_(max=math.log(p / (1.0 - p)))
+                opt.zero_moments("opacities")
+        opt.zero_grad(set_to_none=True)
+        cov6 = cov6_of(free) if cov_moves else cov6_fixed
+        rendered = render_cuda(c2w, Kn, near_t, far_t, (H, W), bg_t, value("means", free)[None].expand(V, -1, -1), cov6[None].expand(V, -1, -1),
+                               value("harmonics", free)[None].expand(V, -1, -1, -1), value("opacities", free)[None].expand(V, -1),
+                               density_stats=stats, return_aux=want_aux)
+        img, dep = rendered[0], rendered[1]
+        opa = _aux_cat(rendered[2], "opacity") if lambdas_depth is not None else None
+        radii = _aux_cat(rendered[2], "radii") if sparse else None
+        if lambdas_depth is None:
+            loss = photometric_loss(img, target, lambda_dssim)
+        else:
+            d_loss = depth_loss(dep, opa, depth_target, depth_conf, depth_mode, depth_space, depth_min_opacity)
+            loss = photometric_loss(img, target, lambda_dssim) + lambdas_depth[it] * d_loss
+        loss.backward()
+        opt.step(visible=radii, lrs=None if means_lrs is None else {"means": means_lrs[it]})
+        if log_every and it % int(log_every) == 0:
+            losses.append(float(loss.detach()))
+            if lambdas_depth is not None:
+                depth_losses.append(float(d_loss.detach()))
     with torch.no_grad():
-        out = {k: (value(k).detach().clone() if k in free else start[k].clone()) for k in FIELDS}
+        out = {k: (value(k, free).detach().clone() if k in free else start[k].clone()) for k in FIELDS}
         out["covariances"] = covariances_from(out["rotations"], out["scales"])
         if density is not None:
             out["density_events"] = events

@@ -5,43 +5,9 @@ import numpy as np
 import pytest
 import torch
 
-from scenes import default_K, look_at_camera, random_scene
+from refine_scenes import BG, FAR, FIELDS, H, NEAR, W, _cams, _psnr, _render, _truth
 
 pytestmark = pytest.mark.gpu
-
-H = W = 128
-NEAR, FAR, BG = 0.5, 100.0, (0.0, 0.0, 0.0)
-FIELDS = ("means", "scales", "rotations", "opacities", "harmonics")
-
-
-def _truth(G=20000, seed=0, scale=(0.01, 0.12)):
-    """random_scene's means / opacities / SH, with seeded scales and RAW (x, y, z, w) quaternions in place of its covariances"""
-    means, _, opac, sh = random_scene(G, seed=seed, n_sh=4)
-    g = torch.Generator().manual_seed(seed + 500)
-    scales = scale[0] + torch.rand(G, 3, generator=g) * (scale[1] - scale[0])
-    rot = torch.randn(G, 4, generator=g) * (0.5 + torch.rand(G, 1, generator=g))  # not normalised
-    return dict(means=means.cuda(), scales=scales.cuda(), rotations=rot.cuda(), opacities=opac.cuda(), harmonics=sh.cuda())
-
-
-def _cams(seeds):
-    c2w = torch.stack([look_at_camera(seed=s) for s in seeds]).cuda()
-    return c2w, default_K()[None].repeat(len(seeds), 1, 1).cuda()
-
-
-def _render(c2w, K, means, cov, sh, opac, aux=False):
-    from siu3r_amd.cuda_splatting import render_cuda
-
-    V = c2w.shape[0]
-    e = lambda x: x[None].expand(V, *x.shape)
-    with torch.no_grad():
-        return render_cuda(c2w, K, torch.full((V,), NEAR), torch.full((V,), FAR), (H, W), torch.zeros(V, 3), e(means), e(cov), e(sh), e(opac),
-                           return_aux=aux)
-
-
-def _psnr(a, b):
-    from siu3r_amd import metrics
-
-    return metrics.psnr(a.permute(1, 2, 0).cpu().numpy(), b.permute(1, 2, 0).cpu().numpy(), data_range=1.0)
 
 
 def _touched(c2w, K, s):
@@ -180,6 +146,39 @@ def test_sparse_steps_with_density_control():
     assert len(losses) == 30 and all(np.isfinite(losses))
     assert out["optimizer_steps"] == 30
     assert all(bool(torch.isfinite(out[k]).all()) for k in FIELDS)
+
+
+def test_sparse_steps_with_a_depth_term():
+    """sparse=True together with depths=: the one iteration whose radii (for the step) and opacity map (for the depth term) come out of the
+    same aux.  A pin that this branch runs, returns the right keys, shapes and step count and leaves the unseen rows alone; a Gaussian
+    no view saw has a zero gradient and zero moments, so a dense step would keep its bits too: that the radii gate the step is
+    pinned by tests/test_gaussian_adam_gpu.py, not here.  Geometry is frozen, so the set of Gaussians the training views see is the
+    same at every iteration."""
+    from siu3r_amd.refine import covariances_from, refine_gaussians
+
+    s = _truth(G=2000)
+    train, Kt = _cams([0, 1])
+    targets, depth, aux = _render(train, Kt, s["means"], covariances_from(s["rotations"], s["scales"]), s["harmonics"], s["opacities"], aux=True)
+    opacity = torch.cat([a["opacity"] for a in aux])
+    conf = (opacity > 0.5).float()
+    depths = torch.where(opacity > 0.5, depth / opacity.clamp_min(1e-6), torch.zeros_like(depth))
+    keep = {k: v.clone() for k, v in s.items()}
+    out, losses = refine_gaussians(*(s[k] for k in FIELDS), targets, train, Kt, NEAR, FAR, BG, iters=3, params=("opacities", "harmonics"), optimizer="hip",
+                                   sparse=True, depths=depths, depth_weights=conf, lambda_depth=1.0)
+    assert len(losses) == 3 and all(np.isfinite(losses))
+    assert len(out["depth_losses"]) == 3 and all(np.isfinite(out["depth_losses"]))
+    assert out["optimizer_steps"] == 3
+    for k in ("means", "scales", "rotations"):
+        assert torch.equal(out[k], keep[k]), f"{k} is frozen and moved"
+    untouched = ~_touched(train, Kt, keep) & ~_touched(train, Kt, out)
+    touched = ~untouched
+    print(f"\nsparse + depth: {int(touched.sum())} of {untouched.numel()} Gaussians touched, losses {losses}, depth term {out['depth_losses']}")
+    assert int(untouched.sum()) > 0 and int(touched.sum()) > 0
+    assert torch.equal(out["harmonics"][untouched], keep["harmonics"][untouched])
+    round_trip = torch.sigmoid(torch.logit(keep["opacities"].clamp(1e-6, 1 - 1e-6)))  # what a free opacity that never moved comes back as
+    assert torch.equal(out["opacities"][untouched], round_trip[untouched])
+    assert not torch.equal(out["harmonics"][touched], keep["harmonics"][touched]), "no touched harmonics row moved"
+    assert not torch.equal(out["opacities"][touched], round_trip[touched]), "no touched opacity moved"
 
 
 def test_torch_path_does_not_report_optimizer_steps():
