@@ -26,7 +26,7 @@ extern "C" {
 #define SIU3R_F64 3
 
 const char* siu3r_last_error(void);
-#define SIU3R_ABI_VERSION 10 /* 10: siu3r_stem7x7_x3 (the Gaussian heads' stem as one dedicated kernel), siu3r_proj_rows_x3 (the heads' last 1 x 1 convolutions as row streams); 9: siu3r_raster_project_c2w + siu3r_raster_cam.k2_near / k2_far (the reference renderer's own pose tensors, consumed on the device), siu3r_raster_tune (replaces the SIU3R_FEAT_FORM / SIU3R_FEAT_NP environment switches; the shared-batch matrix-core composite is gone: no workspace = 32-channel kernel); 8: LPIPS (siu3r_maxpool2x2s2, siu3r_lpips_layer); 7: device-side poses for the gsplat seam (siu3r_raster_project_dp, siu3r_sh_eval_dp, siu3r_blend_background_dp), precomputed K2 colours (sh_degree < 0), all-channel list composite; 6: pre-split bf16x3 activations (siu3r_gemm_params.c_x3 / a_x3, siu3r_gemm_plan_t.a_x3_ok / c_x3_ok), siu3r_attn_params.kv_bxor / kv_x3, siu3r_gemm_params.c_x3_col0; 5: siu3r_raster_sort takes stage 1's counters (culled Gaussians leave the sort), NaN-poisoned views on entry overflow, siu3r_gemm_tune key 4; 4: siu3r_gemm_plan, split-K workspace capacities + self-resetting tickets, tile_cfg; 3: view-batched sort-free rasterizer */
+#define SIU3R_ABI_VERSION 11 /* 11: siu3r_attention_plan (what siu3r_attention launches for a parameter block); 10: siu3r_stem7x7_x3 (the Gaussian heads' stem as one dedicated kernel), siu3r_proj_rows_x3 (the heads' last 1 x 1 convolutions as row streams); 9: siu3r_raster_project_c2w + siu3r_raster_cam.k2_near / k2_far (the reference renderer's own pose tensors, consumed on the device), siu3r_raster_tune (replaces the SIU3R_FEAT_FORM / SIU3R_FEAT_NP environment switches; the shared-batch matrix-core composite is gone: no workspace = 32-channel kernel); 8: LPIPS (siu3r_maxpool2x2s2, siu3r_lpips_layer); 7: device-side poses for the gsplat seam (siu3r_raster_project_dp, siu3r_sh_eval_dp, siu3r_blend_background_dp), precomputed K2 colours (sh_degree < 0), all-channel list composite; 6: pre-split bf16x3 activations (siu3r_gemm_params.c_x3 / a_x3, siu3r_gemm_plan_t.a_x3_ok / c_x3_ok), siu3r_attn_params.kv_bxor / kv_x3, siu3r_gemm_params.c_x3_col0; 5: siu3r_raster_sort takes stage 1's counters (culled Gaussians leave the sort), NaN-poisoned views on entry overflow, siu3r_gemm_tune key 4; 4: siu3r_gemm_plan, split-K workspace capacities + self-resetting tickets, tile_cfg; 3: view-batched sort-free rasterizer */
 int siu3r_abi_version(void);
 
 /* ---- seam 1: curope.rope_2d(tokens, positions, base, fwd)
@@ -195,6 +195,17 @@ int siu3r_attention(const siu3r_attn_params* p, void* stream);
 /* 1 if siu3r_attention would accept these parameters with kv_x3 = 1 (head_dim 64, no mask / RoPE-on-load / key split, >= 64 keys,
  * fp32 + split3, segment-aligned K / V rows), else 0 */
 int siu3r_attention_kv_x3_ok(const siu3r_attn_params* p);
+/* What siu3r_attention will launch for these parameters (same validation, same decision function; launches nothing): the kernel's name
+ * as rocprofv3 prints it -- "siu3r_attn_pipe::attn_pipe_kernel<X3, KVP>" (8-wave pipelined kernel), "attn_fast_kernel<D, MASK, SPLITKV,
+ * X3, KH>" (fast kernels) or "attn_kernel<D, IN_F32, SPLIT, MASK, QKX>" (register-staged kernels: RoPE on load, fp32 tensors without
+ * split3, SIU3R_ATTN_NO_FAST; QKX = 1 with RoPE on load and bf16 operands: the rotated q and k are split for the score product) --, the queries one workgroup covers, the key ranges launched per query tile (splits, else 1), whether
+ * attn_combine_kernel<D> follows, whether wave pairs share 32 queries and take one 32-key half of every tile each, and whether the
+ * pipelined kernel carries query Nq - 1 (Nq = 128 n + 1) as the side path of each problem's last workgroup. */
+typedef struct {
+  char kernel[160];
+  int32_t queries_per_wg, key_ranges, combine, key_halves, side_path;
+} siu3r_attn_plan_t;
+int siu3r_attention_plan(const siu3r_attn_params* p, siu3r_attn_plan_t* out);
 
 /* ---- element-wise / gather kernels (see DESIGN.md for the HBM roofline of each) ---------- */
 /* Contract shared by the entry points of this section, siu3r_layernorm / siu3r_layernorm2 / siu3r_rope2d above and siu3r_split_bf16 below:

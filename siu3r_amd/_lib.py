@@ -67,6 +67,14 @@ class AttnParams(C.Structure):
     ]
 
 
+class AttnPlan(C.Structure):
+    """siu3r_attn_plan_t: what siu3r_attention launches for a parameter block."""
+    _fields_ = [
+        ("kernel", C.c_char * 160), ("queries_per_wg", C.c_int32), ("key_ranges", C.c_int32), ("combine", C.c_int32),
+        ("key_halves", C.c_int32), ("side_path", C.c_int32),
+    ]
+
+
 class RasterCam(C.Structure):
     """siu3r_raster_cam (include/siu3r_hip.h); the CPU oracle's raster_cam has the same layout."""
     _fields_ = [
@@ -92,7 +100,7 @@ class AdamField(C.Structure):
 
 # name -> argtypes; restype is c_int unless listed in _RESTYPES.  Mirrors include/siu3r_hip.h.
 _P, _I, _L, _F = C.c_void_p, C.c_int, C.c_int64, C.c_float
-ABI_VERSION = 10  # SIU3R_ABI_VERSION of include/siu3r_hip.h these ctypes declarations mirror
+ABI_VERSION = 11  # SIU3R_ABI_VERSION of include/siu3r_hip.h these ctypes declarations mirror
 
 SIGNATURES = {
     "siu3r_last_error": [],
@@ -105,6 +113,7 @@ SIGNATURES = {
     "siu3r_layernorm2": [_P, _P, _I, _P, _P, _P, _L, _I, _L, _L, _L, _F, _P],
     "siu3r_attention": [C.POINTER(AttnParams), _P],
     "siu3r_attention_kv_x3_ok": [C.POINTER(AttnParams)],
+    "siu3r_attention_plan": [C.POINTER(AttnParams), C.POINTER(AttnPlan)],
     "siu3r_add": [_P, _P, _P, _L, _L, _I, _P],
     "siu3r_pack_image_nhwc": [_P, _P, _I, _I, _I, _I, _I, _P],
     "siu3r_resize_bilinear": [_P, _I, _P, _I, _P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],

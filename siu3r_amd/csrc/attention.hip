@@ -10,12 +10,18 @@
 // of O^T = V^T P^T using a "virtual k" ordering (key(h,j) = 16*sb + (j&3) + 8*(j>>2) + 4*h); V^T is built in
 // LDS with that same ordering in mind, so no cross-lane shuffle is needed between the two GEMMs.
 // SPLIT = bf16x3 mode: Q,K,P,V are split hi+lo and every product uses three MFMAs (~fp32 accuracy).
+// QKX (bf16 operands, RoPE on load): the ROTATED q and k are fp32 values, and rounding them to bf16 moved a logit of the peaky inputs
+// (|q|, |k| <= 6) by up to 0.13 -- 5e-2 of a near-tie row's output; they are split hi+lo for the score product instead (three MFMAs,
+// K lo plane in LDS), while P and V stay single bf16 planes.
+#include <stdio.h>
 #include <stdlib.h>
+#include <string.h>
 
 #include "common.h"
 
 // attention_pipe.hip: the 8-wave software-pipelined kernel of the ViT blocks
 bool siu3r_attn_pipe_ok(const siu3r_attn_params& p);
+void siu3r_attn_pipe_shape(const siu3r_attn_params& p, int* q_tiles, int* has_x);
 int siu3r_attn_pipe_launch(const siu3r_attn_params& p, hipStream_t s);
 
 namespace {
@@ -30,12 +36,13 @@ __device__ __forceinline__ int k_off(int row, int chunk) {
   return row * 64 + ((chunk ^ ((row >> 2) & 3)) << 4);
 }
 
-template <int D, int IN_F32, int SPLIT, int MASK>
+template <int D, int IN_F32, int SPLIT, int MASK, int QKX = 0>
 __global__ __launch_bounds__(256) void attn_kernel(const siu3r_attn_params p) {
-  constexpr int PL = SPLIT ? 2 : 1;
+  static_assert(!(SPLIT && QKX), "bf16x3 splits q and k anyway");
+  constexpr bool KX = SPLIT || QKX;  // q and k as hi + lo planes
   constexpr int K_BYTES = KT * D * 2;
   constexpr int V_BYTES = D * VT_STRIDE;
-  constexpr int STAGE = PL * (K_BYTES + V_BYTES);
+  constexpr int STAGE = K_BYTES + V_BYTES + (KX ? K_BYTES : 0) + (SPLIT ? V_BYTES : 0);  // [K | V | K lo | V lo]
   constexpr int CH = D / 32;  // chunks (8 elements) per thread per tile: 64 keys * D/8 chunks / 256 threads
   constexpr int KS = D / 16;  // k-substeps of the score GEMM
   constexpr int DT = D / 32;  // 32-row output tiles of O^T
@@ -84,7 +91,7 @@ __global__ __launch_bounds__(256) void attn_kernel(const siu3r_attn_params p) {
     }
 #pragma unroll
     for (int ks = 0; ks < KS; ++ks) {
-      if (SPLIT) {
+      if (KX) {
         uint4 hi, lo;
         split_bf16x8(qv[ks], hi, lo);
         qf[ks] = as_bf16x8(hi);
@@ -172,7 +179,7 @@ __global__ __launch_bounds__(256) void attn_kernel(const siu3r_attn_params p) {
     for (int c = 0; c < CH; ++c) {
       const int ch = ld_c0 + 2 * c;
       const int ko = k_off<D>(ld_key, ch);
-      if (SPLIT) {
+      if (KX) {
         uint4 hi, lo;
         split_bf16x8(kreg[c], hi, lo);
         *(uint4*)(sK + ko) = hi;
@@ -227,7 +234,7 @@ __global__ __launch_bounds__(256) void attn_kernel(const siu3r_attn_params p) {
       for (int ks = 0; ks < KS; ++ks) {
         const int o = k_off<D>(kb * 32 + l31, ks * 2 + lh);
         const bf16x8 kf = as_bf16x8(*(const uint4*)(sK + o));
-        if (SPLIT) {
+        if (KX) {
           const bf16x8 kfl = as_bf16x8(*(const uint4*)(sKl + o));
           sacc[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kfl, qf[ks], sacc[kb], 0, 0, 0);
           sacc[kb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qfl[ks], sacc[kb], 0, 0, 0);
@@ -577,7 +584,12 @@ __global__ __launch_bounds__(256) void attn_fast_kernel(const siu3r_attn_params 
       m_run = m_new;
     }
     float psum = 0.f;
-    const float nm = -m_run * sl2;  // exp2((s - m) * sl2) as one fma + v_exp_f32 per score; m tracks the RAW maximum
+    float nm = -m_run * sl2;  // exp2((s - m) * sl2) as one fma + v_exp_f32 per score; m tracks the RAW maximum
+    // A row whose keys so far are all masked still has m_run == NEG_BIG, and fma(NEG_BIG, sl2, nm) is then the ROUNDING ERROR of nm, of
+    // the order 1e22 with either sign: exp2 of it is 0 or +inf by the luck of the scale (head_dim 32: 0; head_dim 64: +inf, and the
+    // alpha = 0 of the first admitted key turns inf into NaN).  Such a row takes weight 0 until a key is admitted.  (Only a mask can
+    // block a whole first block: without one every wave's first key block holds a valid key.)
+    if constexpr (MASK) nm = m_run == NEG_BIG ? 0.f : nm;
 #pragma unroll
     for (int j = 0; j < NKB; ++j)
 #pragma unroll
@@ -690,7 +702,7 @@ __global__ __launch_bounds__(256) void attn_fast_kernel(const siu3r_attn_params 
           oacc[dt][4 * g + e] = oacc[dt][4 * g + e] * w0 + xs[l31 * (D + 2) + dt * 32 + 8 * g + 4 * lh + e] * w1;
   }
   if (SPLITKV) {
-    // partial result of this key range: un-normalised O (relative to m_run), m_run and l; an empty range contributes
+    // partial result of this key range: un-normalised O (relative to m_run), m_run and l; an empty or fully masked range contributes
     // (NEG_BIG, 0, 0), which the combine step weights by exp2(-inf) = 0
     const int64_t nqp = (int64_t)((p.Nq + 127) / 128) * 128;
     float* w = p.ws + ((((int64_t)b * p.H + h) * p.splits + k_split) * nqp + q_row) * (D + 4);
@@ -770,25 +782,77 @@ __global__ void attn_combine_kernel(const siu3r_attn_params p) {
 // measured (tools/mb_attn.py): bf16 108 workgroups 22.9 -> 18.4 us, 288 workgroups 36.0 -> 39.0 us; bf16x3 288 workgroups 78 -> 70 us
 static const int64_t g_attn_kh_max = getenv("SIU3R_ATTN_KH_MAX") ? atoll(getenv("SIU3R_ATTN_KH_MAX")) : -1;
 
+// ---- what to launch.  One decision function for siu3r_attention and siu3r_attention_plan: kernel family, template arguments, key
+// halves or key ranges, and the side path of the pipelined kernel.
+enum { FAM_PIPE = 0, FAM_FAST = 1, FAM_STAGED = 2 };
+struct attn_route {
+  int family;
+  int x3;       // pipe / fast: X3; staged: SPLIT
+  int in_f32;   // staged: IN_F32
+  int mask;     // fast / staged: MASK
+  int splitkv;  // fast: SPLITKV (key ranges + combine kernel)
+  int kh;       // fast: KH (64-query workgroups, wave pairs split every key tile)
+  int kvp;      // pipe: KVP (pre-split K / V planes)
+  int qkx;      // staged: QKX (RoPE on load with bf16 operands: rotated q, k split for the score product)
+  int side;     // pipe: the last workgroup of a problem carries query Nq - 1 as its side path
+  int q_tiles;  // pipe: query tiles per (batch, head) problem
+};
+
+bool attn_no_fast() {
+  static const bool v = getenv("SIU3R_ATTN_NO_FAST") != nullptr;  // A/B switch
+  return v;
+}
+
+void attn_route_of(const siu3r_attn_params& p, attn_route& r) {
+  r = attn_route{};
+  const bool no_fast = attn_no_fast();
+  if (!no_fast && siu3r_attn_pipe_ok(p)) {
+    r.family = FAM_PIPE;
+    r.x3 = p.dtype == SIU3R_F32;
+    r.kvp = p.dtype == SIU3R_F32 && p.kv_x3;
+    siu3r_attn_pipe_shape(p, &r.q_tiles, &r.side);
+    return;
+  }
+  const bool fast_bf16 = p.dtype == SIU3R_BF16 && !p.split3 && !p.rope_cos && !no_fast;
+  const bool fast_x3 = p.dtype == SIU3R_F32 && p.split3 && !p.rope_cos && !no_fast;
+  if (fast_bf16 || fast_x3) {
+    r.family = FAM_FAST;
+    r.x3 = fast_x3;
+    r.mask = p.mask != nullptr;
+    const int qtiles = (p.Nq + 127) / 128;
+    if (p.splits > 1 && p.ws) {
+      r.splitkv = 1;
+    } else if (!p.mask && p.Nk >= 64 && (int64_t)qtiles * p.H * p.B < (g_attn_kh_max >= 0 ? g_attn_kh_max : (r.x3 ? 512 : 256))) {
+      // too few 128-query workgroups to give every SIMD two waves: 64-query workgroups whose wave pairs split each key tile
+      r.kh = 1;
+    }
+    return;
+  }
+  r.family = FAM_STAGED;
+  r.x3 = p.split3 != 0;
+  r.in_f32 = p.split3 || p.dtype == SIU3R_F32;
+  r.mask = p.mask != nullptr;
+  r.qkx = p.rope_cos != nullptr && !r.x3;  // (RoPE on load: head_dim 64, by validation)
+}
+
 template <int D, int X3>
-int launch_fast(const siu3r_attn_params& p, hipStream_t s) {
+int launch_fast(const siu3r_attn_params& p, const attn_route& r, hipStream_t s) {
   dim3 block(256);
   const int qtiles = (p.Nq + 127) / 128;
-  if (p.splits > 1 && p.ws) {
+  if (r.splitkv) {
     dim3 grid(qtiles * p.splits, p.H, p.B);
-    if (p.mask)
+    if (r.mask)
       hipLaunchKernelGGL((attn_fast_kernel<D, 1, 1, X3>), grid, block, 0, s, p);
     else
       hipLaunchKernelGGL((attn_fast_kernel<D, 0, 1, X3>), grid, block, 0, s, p);
     const int64_t n = (int64_t)p.B * p.H * p.Nq * (D / 4);
     hipLaunchKernelGGL((attn_combine_kernel<D>), dim3((unsigned)((n + 255) / 256)), block, 0, s, p);
-  } else if (!p.mask && p.Nk >= 64 && (int64_t)qtiles * p.H * p.B < (g_attn_kh_max >= 0 ? g_attn_kh_max : (X3 ? 512 : 256))) {
-    // too few 128-query workgroups to give every SIMD two waves: 64-query workgroups whose wave pairs split each key tile
+  } else if (r.kh) {
     dim3 grid((p.Nq + 63) / 64, p.H, p.B);
     hipLaunchKernelGGL((attn_fast_kernel<D, 0, 0, X3, 1>), grid, block, 0, s, p);
   } else {
     dim3 grid(qtiles, p.H, p.B);
-    if (p.mask)
+    if (r.mask)
       hipLaunchKernelGGL((attn_fast_kernel<D, 1, 0, X3>), grid, block, 0, s, p);
     else
       hipLaunchKernelGGL((attn_fast_kernel<D, 0, 0, X3>), grid, block, 0, s, p);
@@ -798,9 +862,19 @@ int launch_fast(const siu3r_attn_params& p, hipStream_t s) {
 }
 
 template <int D, int IN_F32, int SPLIT>
-int launch(const siu3r_attn_params& p, hipStream_t s) {
+int launch(const siu3r_attn_params& p, const attn_route& r, hipStream_t s) {
   dim3 grid((p.Nq + 127) / 128, p.H, p.B), block(256);
-  if (p.mask)
+  if constexpr (D == 64 && !SPLIT) {
+    if (r.qkx) {
+      if (r.mask)
+        hipLaunchKernelGGL((attn_kernel<D, IN_F32, SPLIT, 1, 1>), grid, block, 0, s, p);
+      else
+        hipLaunchKernelGGL((attn_kernel<D, IN_F32, SPLIT, 0, 1>), grid, block, 0, s, p);
+      SIU3R_LAUNCH_CHECK("siu3r_attention");
+      return 0;
+    }
+  }
+  if (r.mask)
     hipLaunchKernelGGL((attn_kernel<D, IN_F32, SPLIT, 1>), grid, block, 0, s, p);
   else
     hipLaunchKernelGGL((attn_kernel<D, IN_F32, SPLIT, 0>), grid, block, 0, s, p);
@@ -811,17 +885,16 @@ int launch(const siu3r_attn_params& p, hipStream_t s) {
 }  // namespace
 
 static bool kv_x3_ok(const siu3r_attn_params& p) {
-  static const bool no_fast = getenv("SIU3R_ATTN_NO_FAST") != nullptr;
   // whole segments: a head's 64 dims start on a 32-column boundary of the projection output, rows and batch items likewise
   const bool seg = p.k_sh % 32 == 0 && p.k_sn % 32 == 0 && p.k_sb % 32 == 0 && p.v_sh % 32 == 0 && p.v_sn % 32 == 0 && p.v_sb % 32 == 0 &&
                    ((uintptr_t)p.k % 128) == 0 && ((uintptr_t)p.v % 128) == 0;
-  return !no_fast && p.dtype == SIU3R_F32 && p.split3 && seg && siu3r_attn_pipe_ok(p);
+  return !attn_no_fast() && p.dtype == SIU3R_F32 && p.split3 && seg && siu3r_attn_pipe_ok(p);
 }
 
 extern "C" int siu3r_attention_kv_x3_ok(const siu3r_attn_params* pp) { return pp && kv_x3_ok(*pp) ? 1 : 0; }
 
-extern "C" int siu3r_attention(const siu3r_attn_params* pp, void* stream) {
-  const siu3r_attn_params& p = *pp;
+// parameter validation shared by siu3r_attention and siu3r_attention_plan
+static int validate_attn(const siu3r_attn_params& p) {
   SIU3R_CHECK(p.q && p.k && p.v && p.out, "siu3r_attention: null pointer");
   SIU3R_CHECK(p.D == 64 || p.D == 32, "siu3r_attention: head_dim %d unsupported (32 or 64)", p.D);
   SIU3R_CHECK(p.B > 0 && p.H > 0 && p.Nq > 0 && p.Nk > 0, "siu3r_attention: empty problem");
@@ -839,18 +912,55 @@ extern "C" int siu3r_attention(const siu3r_attn_params* pp, void* stream) {
               "siu3r_attention: q/k/v strides must keep 16-byte alignment");
   SIU3R_CHECK(!p.kv_x3 || kv_x3_ok(p), "siu3r_attention: kv_x3 (pre-split K / V planes) needs the pipelined bf16x3 kernel (head_dim 64, no mask / RoPE on load / "
               "key split, >= 64 keys) and segment-aligned K / V: query siu3r_attention_kv_x3_ok first");
-  hipStream_t s = (hipStream_t)stream;
-  static const bool no_fast = getenv("SIU3R_ATTN_NO_FAST") != nullptr;  // A/B switch
-  if (!no_fast && siu3r_attn_pipe_ok(p)) return siu3r_attn_pipe_launch(p, s);
-  if (p.dtype == SIU3R_BF16 && !p.split3 && !p.rope_cos && !no_fast) return p.D == 64 ? launch_fast<64, 0>(p, s) : launch_fast<32, 0>(p, s);
-  if (p.dtype == SIU3R_F32 && p.split3 && !p.rope_cos && !no_fast) return p.D == 64 ? launch_fast<64, 1>(p, s) : launch_fast<32, 1>(p, s);
-  if (p.D == 64) {
-    if (p.split3) return launch<64, 1, 1>(p, s);
-    if (p.dtype == SIU3R_F32) return launch<64, 1, 0>(p, s);
-    return launch<64, 0, 0>(p, s);
+  return 0;
+}
+
+extern "C" int siu3r_attention_plan(const siu3r_attn_params* pp, siu3r_attn_plan_t* out) {
+  SIU3R_CHECK(pp && out, "siu3r_attention_plan: null argument");
+  const siu3r_attn_params& p = *pp;
+  if (int rc = validate_attn(p)) return rc;
+  attn_route r;
+  attn_route_of(p, r);
+  memset(out, 0, sizeof(*out));
+  out->key_ranges = 1;
+  if (r.family == FAM_PIPE) {
+    snprintf(out->kernel, sizeof(out->kernel), "siu3r_attn_pipe::attn_pipe_kernel<%s, %s>", r.x3 ? "true" : "false", r.kvp ? "true" : "false");
+    out->queries_per_wg = 128;
+    out->key_halves = 1;
+    out->side_path = r.side;
+  } else if (r.family == FAM_FAST) {
+    snprintf(out->kernel, sizeof(out->kernel), "attn_fast_kernel<%d, %d, %d, %d, %d>", p.D, r.mask, r.splitkv, r.x3, r.kh);
+    out->queries_per_wg = r.kh ? 64 : 128;
+    out->key_halves = r.kh;
+    if (r.splitkv) {
+      out->key_ranges = p.splits;
+      out->combine = 1;
+    }
   } else {
-    if (p.split3) return launch<32, 1, 1>(p, s);
-    if (p.dtype == SIU3R_F32) return launch<32, 1, 0>(p, s);
-    return launch<32, 0, 0>(p, s);
+    snprintf(out->kernel, sizeof(out->kernel), "attn_kernel<%d, %d, %d, %d, %d>", p.D, r.in_f32, r.x3, r.mask, r.qkx);
+    out->queries_per_wg = 128;
+  }
+  return 0;
+}
+
+extern "C" int siu3r_attention(const siu3r_attn_params* pp, void* stream) {
+  const siu3r_attn_params& p = *pp;
+  if (int rc = validate_attn(p)) return rc;
+  attn_route r;
+  attn_route_of(p, r);
+  hipStream_t s = (hipStream_t)stream;
+  if (r.family == FAM_PIPE) return siu3r_attn_pipe_launch(p, s);
+  if (r.family == FAM_FAST) {
+    if (r.x3) return p.D == 64 ? launch_fast<64, 1>(p, r, s) : launch_fast<32, 1>(p, r, s);
+    return p.D == 64 ? launch_fast<64, 0>(p, r, s) : launch_fast<32, 0>(p, r, s);
+  }
+  if (p.D == 64) {
+    if (r.x3) return launch<64, 1, 1>(p, r, s);
+    if (r.in_f32) return launch<64, 1, 0>(p, r, s);
+    return launch<64, 0, 0>(p, r, s);
+  } else {
+    if (r.x3) return launch<32, 1, 1>(p, r, s);
+    if (r.in_f32) return launch<32, 1, 0>(p, r, s);
+    return launch<32, 0, 0>(p, r, s);
   }
 }

@@ -546,10 +546,17 @@ bool siu3r_attn_pipe_ok(const siu3r_attn_params& p) {
   return bf16_mode == 1 || (int64_t)((p.Nq + siu3r_attn_pipe::QT - 1) / siu3r_attn_pipe::QT) * p.H * p.B >= 192;
 }
 
+// query tiles per (batch, head) problem, and whether the last one carries query Nq - 1 (Nq = 128 n + 1) as its side path
+void siu3r_attn_pipe_shape(const siu3r_attn_params& p, int* q_tiles, int* has_x) {
+  using namespace siu3r_attn_pipe;
+  *has_x = (p.Nq > QT && (p.Nq & (QT - 1)) == 1) ? 1 : 0;
+  *q_tiles = *has_x ? (p.Nq - 1) / QT : (p.Nq + QT - 1) / QT;
+}
+
 int siu3r_attn_pipe_launch(const siu3r_attn_params& p, hipStream_t s) {
   using namespace siu3r_attn_pipe;
-  const int has_x = (p.Nq > QT && (p.Nq & (QT - 1)) == 1) ? 1 : 0;
-  const int q_tiles = has_x ? (p.Nq - 1) / QT : (p.Nq + QT - 1) / QT;
+  int q_tiles, has_x;
+  siu3r_attn_pipe_shape(p, &q_tiles, &has_x);
   const dim3 grid((unsigned)(q_tiles * p.H * p.B)), block(NT);
   if (p.dtype == SIU3R_F32 && p.kv_x3)
     hipLaunchKernelGGL((attn_pipe_kernel<true, true>), grid, block, 0, s, p, q_tiles, has_x);

@@ -697,14 +697,17 @@ _ATTN_SPLITKV = __import__("os").environ.get("SIU3R_NO_ATTN_SPLITKV", "0") != "1
 
 
 def attention(q, k, v, *, heads: int, head_dim: int, scale: float, rope=None, qpos=None, kpos=None,
-              mask: Optional[torch.Tensor] = None, split3=False, kv_bxor: int = 0, kv_planes: bool = False, dry_run: bool = False):
+              mask: Optional[torch.Tensor] = None, split3=False, kv_bxor: int = 0, kv_planes: bool = False, dry_run: bool = False,
+              plan: bool = False):
     """q [B,Nq,H,D] / k,v [B,Nk,H,D] strided views (D contiguous) -> out [B,Nq,H*D].  kv_bxor: batch item b attends to the keys / values
     of batch item b ^ kv_bxor (siu3r_attn_params.kv_bxor).  kv_planes: k and v are views of PRE-SPLIT planes (a projection written with
-    planes_from_col); dry_run: launch nothing, return whether this launch could read such planes (siu3r_attention_kv_x3_ok)."""
+    planes_from_col); dry_run: launch nothing, return whether this launch could read such planes (siu3r_attention_kv_x3_ok).
+    plan: launch nothing, return the siu3r_attn_plan_t of this launch (siu3r_attention_plan: kernel name, queries per workgroup, key
+    ranges, combine pass), or raise what the launch would raise."""
     _gpu(q, k, v, mask)
     B, Nq = q.shape[0], q.shape[1]
     Nk = k.shape[1]
-    out = q if dry_run else torch.empty((B, Nq, heads * head_dim), dtype=q.dtype, device=q.device)  # (a dry run only needs a non-null pointer)
+    out = q if dry_run or plan else torch.empty((B, Nq, heads * head_dim), dtype=q.dtype, device=q.device)  # (a dry run only needs a non-null pointer)
     p = AttnParams()
     p.q, p.k, p.v, p.out = _p(q), _p(k), _p(v), _p(out)
     p.dtype = _dt(q)
@@ -741,8 +744,17 @@ def attention(q, k, v, *, heads: int, head_dim: int, scale: float, rope=None, qp
             p.ws = _p(ws)
     if dry_run:  # (asked of exactly the parameter block the launch would carry, key split included)
         return bool(_lib.lib().siu3r_attention_kv_x3_ok(C.byref(p))) and not _NO_PRESPLIT
+    if plan:  # (likewise: splits and ws are set as for the launch)
+        pl = _lib.AttnPlan()
+        check(_lib.lib().siu3r_attention_plan(C.byref(p), C.byref(pl)))
+        return pl
     check(_lib.lib().siu3r_attention(C.byref(p), _stream()))
     return out
+
+
+def attention_plan(q, k, v, **kw):
+    """ops.attention(..., plan=True): what the launch with these arguments would run"""
+    return attention(q, k, v, plan=True, **kw)
 
 
 def layernorm2(x: torch.Tensor, gamma, beta, eps: float):

@@ -28,18 +28,18 @@ def test_library_exports_every_declared_symbol():
         assert hasattr(l, s), f"{s} declared in include/siu3r_hip.h but not exported"
         assert s in _lib.SIGNATURES, f"{s} has no ctypes signature"
     assert set(_lib.SIGNATURES) <= set(syms) | {"siu3r_last_error", "siu3r_abi_version"}
-    assert l.siu3r_abi_version() == _lib.ABI_VERSION == 10
+    assert l.siu3r_abi_version() == _lib.ABI_VERSION == 11
 
 
 def test_struct_layouts_match_c():
     """sizeof of the ctypes mirrors == sizeof of the C structs (compiled with the host compiler)."""
     from siu3r_amd import _lib
 
-    src = '#include <stdio.h>\n#include "siu3r_hip.h"\nint main(){printf("%zu %zu %zu\\n", sizeof(siu3r_gemm_params), sizeof(siu3r_attn_params), sizeof(siu3r_raster_cam));return 0;}\n'
+    src = '#include <stdio.h>\n#include "siu3r_hip.h"\nint main(){printf("%zu %zu %zu %zu\\n", sizeof(siu3r_gemm_params), sizeof(siu3r_attn_params), sizeof(siu3r_raster_cam), sizeof(siu3r_attn_plan_t));return 0;}\n'
     exe = "/tmp/siu3r_sizeof"
     subprocess.run(["gcc", "-x", "c", "-", "-I", os.path.join(ROOT, "include"), "-o", exe], input=src.encode(), check=True)
     sizes = list(map(int, subprocess.run([exe], capture_output=True, check=True).stdout.split()))
-    assert sizes == [C.sizeof(_lib.GemmParams), C.sizeof(_lib.AttnParams), C.sizeof(_lib.RasterCam)], sizes
+    assert sizes == [C.sizeof(_lib.GemmParams), C.sizeof(_lib.AttnParams), C.sizeof(_lib.RasterCam), C.sizeof(_lib.AttnPlan)], sizes
 
 
 def test_oracle_raster_struct_matches():
