@@ -545,91 +545,6 @@ class AsymmetricCroCoMulti(AsymmetricCroCo):
 # ==================================================================================================
 # DPT heads (heads/dpt_block.py, dpt_head.py:36-79, dpt_gs_head.py:121-171)
 # ==================================================================================================
-class _DPTHead:
-    def __init__(self, ctx: _Ctx, prefix: str, gs: bool):
-        self.ctx, self.p, self.gs = ctx, prefix, gs
-
-    def _rcu(self, q, x, extra=None):
-        """ResidualConvUnit_custom (dpt_block.py:126-147): conv2(relu(conv1(relu(x)))) + x (+ extra)."""
-        ctx = self.ctx
-        o = ops.conv2d(x, ctx.w.conv(q + ".conv1"), pad=1, out_dtype=ctx.act, act=ACT_RELU, relu_in=True)
-        res = x if extra is None else ops.affine_add(x, extra, None, None)
-        return ops.conv2d(o, ctx.w.conv(q + ".conv2"), pad=1, out_dtype=ctx.act, residual=res)
-
-    def _fusion(self, q, x0, x1):
-        """FeatureFusionBlock_custom.forward (dpt_block.py:198-237).  out_conv (1x1) commutes with the
-        align_corners=True bilinear x2 (both linear, weights sum to 1), so it runs at the low resolution."""
-        ctx = self.ctx
-        out = x0 if x1 is None else self._rcu(q + ".resConfUnit1", x1, extra=x0)
-        out = self._rcu(q + ".resConfUnit2", out)
-        out = ops.linear(out, ctx.w.linear(q + ".out_conv"), out_dtype=ctx.act)
-        B, hh, ww, Cc = out.shape
-        return ops.resize_bilinear(out, (2 * hh, 2 * ww), True)
-
-    def trunk(self, tokens: Sequence[torch.Tensor], H, W):
-        ctx, p = self.ctx, self.p
-        nh, nw = H // 16, W // 16
-        layers = []
-        for i, hk in enumerate(DPT_HOOKS):
-            t = tokens[hk]  # [B, N, C] fp32 strided view
-            B = t.shape[0]
-            a = f"{p}.dpt.act_postprocess.{i}"
-            l = ops.linear(t, ctx.w.linear(a + ".0"), out_dtype=ctx.act).view(B, nh, nw, -1)
-            if i in (0, 1):
-                l = ops.conv_transpose2d(l, ctx.w.convT(a + ".1"), out_dtype=ctx.act)
-            elif i == 3:
-                l = ops.conv2d(l, ctx.w.conv(a + ".1"), stride=2, pad=1, out_dtype=ctx.act)
-            l = ops.conv2d(l, ctx.w.conv(f"{p}.dpt.scratch.layer_rn.{i}"), pad=1, out_dtype=ctx.act)
-            layers.append(l)
-        s = f"{p}.dpt.scratch"
-        path4 = self._fusion(s + ".refinenet4", layers[3], None)
-        path3 = self._fusion(s + ".refinenet3", path4, layers[2])
-        path2 = self._fusion(s + ".refinenet2", path3, layers[1])
-        return self._fusion(s + ".refinenet1", path2, layers[0])
-
-    def forward_pts3d(self, tokens, H, W):
-        """PixelwiseTaskWithDPT.forward + postprocess 'exp' (dpt_head.py:113-120; postprocess.py:45-61)."""
-        ctx, p = self.ctx, self.p
-        x = self.trunk(tokens, H, W)
-        x = ops.conv2d(x, ctx.w.conv(f"{p}.dpt.head.0"), pad=1, out_dtype=ctx.act)
-        x = ops.resize_bilinear(x, (H, W), True)
-        x = ops.conv2d(x, ctx.w.conv(f"{p}.dpt.head.2"), pad=1, out_dtype=ctx.act, act=ACT_RELU)
-        xyz = _head4(ctx, (f"{p}.dpt.head.4",), x.view(x.shape[0], 1, H * W, x.shape[-1]))
-        xyz = ops.linear(x, ctx.w.linear(f"{p}.dpt.head.4"), out_dtype=torch.float32) if xyz is None else xyz.view(x.shape[0], H, W, -1)
-        return {"pts3d": ops.pts3d_exp_(xyz)}
-
-    def forward_gs(self, tokens, img_nhwc8, H, W, out=None):
-        """dpt_gs_head.py:121-171: feat_up(path_1) + ReLU(conv7x7(img)) fused into the 7x7 conv's epilogue.
-        out: optional [B, H*W, 83] fp32 destination (a view of the model's [B, V, H*W, 83] raw-Gaussian buffer)."""
-        ctx, p = self.ctx, self.p
-        path1 = self.trunk(tokens, H, W)
-        if _stem_kernel_ok(ctx, img_nhwc8, path1, H, W):  # the dedicated stem kernel (csrc/stem.hip), planes when head.0's plan reads them
-            Bn = img_nhwc8.shape[0]
-            x = torch.empty((Bn, H, W, 256), dtype=torch.float32, device=ctx.dev)
-            w0 = ctx.w.conv(f"{p}.dpt.head.0")
-            xp = ops.Planes(x, storage=x) if _CONV_PLANES else None
-            reads = xp is not None and not ops._NO_PRESPLIT and bool(ops.conv2d(x, w0, pad=1, act=ACT_RELU, dry_run=True).a_x3_ok)
-            wf, wb = ctx.w.stem7((f"{p}.dpt.input_merger.0",))
-            ops.stem7x7_x3(img_nhwc8.view(Bn, 1, H, W, 4), wf, wb, path1.view(Bn, 1, H // 2, W // 2, 256), x.view(Bn, 1, H, W, 256), planes=reads)
-            if reads:
-                xp.valid = xp.only = True
-            x = ops.conv2d(x, w0, pad=1, out_dtype=ctx.act, act=ACT_RELU, a_planes=xp if reads else None)
-        else:
-            x = ops.conv2d(img_nhwc8, ctx.w.conv(f"{p}.dpt.input_merger.0", cin_pad=ops.image_channels(ctx.split)), pad=3, out_dtype=ctx.act,
-                           act=ACT_RELU, up_src=path1)
-            x = ops.conv2d(x, ctx.w.conv(f"{p}.dpt.head.0"), pad=1, out_dtype=ctx.act, act=ACT_RELU)
-        Bn = x.shape[0]
-        if out is not None and out.stride(2) == 1:  # [B, H*W, 83]: one view of every batch item of the raw-Gaussian buffer
-            if _head4(ctx, (f"{p}.dpt.head.4",), x.view(Bn, 1, H * W, x.shape[-1]), out=out.unsqueeze(1)) is not None:
-                return out
-        if out is not None:
-            return ops.linear(x.view(x.shape[0], H * W, -1), ctx.w.linear(f"{p}.dpt.head.4"), out=out)
-        r = _head4(ctx, (f"{p}.dpt.head.4",), x.view(Bn, 1, H * W, x.shape[-1]))
-        if r is not None:
-            return r.view(Bn, H, W, -1)
-        return ops.linear(x, ctx.w.linear(f"{p}.dpt.head.4"), out_dtype=torch.float32)  # [B,H,W,83]
-
-
 _PROJ_KERNEL = os.environ.get("SIU3R_NO_PROJ_KERNEL", "0") != "1"  # A/B switch: the heads' last 1 x 1 convolutions on the GEMM again
 
 
@@ -655,113 +570,144 @@ def _stem_kernel_ok(ctx, img, path1, H, W) -> bool:
             and path1.shape[-1] == 256 and path1.is_contiguous() and H % 16 == 0 and W % 16 == 0)
 
 
-class _DPTHeadPair:
-    """The two DPT heads of a kind (head1 on view 0, head2 on view 1: reference model.py:352-375 runs them one after the other) as ONE
-    sequence of grouped launches: activations [B, 2, h, w, C], every convolution / linear multiplies image (b, g) by the weights of head
-    g (blockIdx.z = b * 2 + g).  Same arithmetic per head as _DPTHead; half the launches, twice the tiles per launch -- the trunk's
-    convolutions at 16^2 .. 128^2 are a fraction of the 256 CUs each on their own.  Used for V == 2, B == 1 (the stem of the Gaussian
-    head reads its upsample source per head and stays two launches)."""
+class _DPTHeads:
+    """One DPT head (prefixes = (name,)): activations [B, h, w, C], plain launches.  Or the G heads of a kind (head1 on view 0, head2 on
+    view 1: reference model.py:352-375 runs them one after the other) as ONE sequence of grouped launches: activations [B, G, h, w, C],
+    every convolution / linear multiplies image (b, g) by the weights of head g (blockIdx.z = b * G + g).  Same arithmetic per head;
+    half the launches, twice the tiles per launch -- the trunk's convolutions at 16^2 .. 128^2 are a fraction of the 256 CUs each on
+    their own.  Grouped for V == 2, B == 1.  Below, `lead` is (B,) or (B, G) and every view is written against it."""
 
     def __init__(self, ctx: _Ctx, prefixes: Sequence[str], gs: bool):
         self.ctx, self.ps, self.gs = ctx, tuple(prefixes), gs
+        self.grouped = len(self.ps) > 1
 
-    def _w(self, kind: str, name: str, **kw):
-        """layer `name` (relative to the head prefix) of both heads as one grouped weight"""
+    def _w(self, kind: str, name: str):
+        """layer `name` (relative to the head prefix): the head's packed weight, or that of all heads as one grouped weight"""
         w = self.ctx.w
-        build = {"conv": lambda q: w.conv(q + name, **kw), "convT": lambda q: w.convT(q + name), "linear": lambda q: w.linear(q + name)}[kind]
-        return w.group("pair:" + "|".join(self.ps) + ":" + name, build, self.ps)
+        if not self.grouped:
+            return getattr(w, kind)(self.ps[0] + name)
+        return w.group("pair:" + "|".join(self.ps) + ":" + name, lambda q: getattr(w, kind)(q + name), self.ps)
+
+    # Where the grouped heads launch something else than a single head, on purpose (what each ran before they shared this class; making
+    # them uniform changes what B > 1 and V > 2 run, which wants its own measurement):
+    def _rcu_planes(self) -> bool:
+        """1. a residual unit's conv1 writes pre-split planes for its conv2: grouped only"""
+        return self.grouped and self.ctx.split and _CONV_PLANES
+
+    def _stem_kernel_planes(self) -> bool:
+        """2. the stem kernel writes pre-split planes for head.0: both (grouped would add ctx.split, which _stem_kernel_ok implies)"""
+        return _CONV_PLANES and not ops._NO_PRESPLIT
+
+    def _stem_gemm_planes(self) -> bool:
+        """3. the GEMM stems (7 x 7 with up_src) write pre-split planes for head.0: grouped only (and it asks head.0's plan before it
+        knows which stem runs)"""
+        return self.grouped and self.ctx.split and _CONV_PLANES
 
     def _rcu(self, q, x, extra=None):
+        """ResidualConvUnit_custom (dpt_block.py:126-147): conv2(relu(conv1(relu(x)))) + x (+ extra)."""
         ctx = self.ctx
-        w1, w2 = self._w("conv", q + ".conv1"), self._w("conv", q + ".conv2")
-        res = x if extra is None else ops.affine_add(x.flatten(0, 1), extra.flatten(0, 1), None, None).view(x.shape)
-        if not (ctx.split and _CONV_PLANES):
-            o = ops.conv2d_grouped(x, w1, pad=1, out_dtype=ctx.act, act=ACT_RELU, relu_in=True)
-            return ops.conv2d_grouped(o, w2, pad=1, out_dtype=ctx.act, residual=res)
-        # bf16x3: conv1's ReLU'd output feeds conv2 only -- written as pre-split planes (ops.Planes) when conv2's plan reads them
-        o = torch.empty(x.shape[:-1] + (w1.n,), dtype=torch.float32, device=x.device)
-        op = ops.Planes(o, storage=o)
-        reads = bool(ops.conv2d_grouped(o, w2, pad=1, residual=res, dry_run=True).a_x3_ok)
-        ops.conv2d_grouped(x, w1, pad=1, act=ACT_RELU, relu_in=True, out=o, planes_out=op if reads else None, planes_only=True)
-        return ops.conv2d_grouped(o, w2, pad=1, residual=res, a_planes=op if reads else None)
+        W = lambda name: self._w("conv", q + name)
+        skip = lambda: x if extra is None else ops.affine_add(x.flatten(0, -4), extra.flatten(0, -4), None, None).view(x.shape)
+        if self.grouped:  # (order only, as it was: grouped packs both weights and adds `extra` before conv1, a single head behind conv1)
+            W(".conv1"), W(".conv2")
+            res = skip()
+        if self._rcu_planes():
+            # bf16x3: conv1's ReLU'd output feeds conv2 only -- written as pre-split planes (ops.Planes) when conv2's plan reads them
+            o = torch.empty(x.shape[:-1] + (W(".conv1").n,), dtype=torch.float32, device=x.device)
+            op = ops.Planes(o, storage=o)
+            reads = bool(ops.conv2d(o, W(".conv2"), pad=1, residual=res, dry_run=True).a_x3_ok)
+            ops.conv2d(x, W(".conv1"), pad=1, act=ACT_RELU, relu_in=True, out=o, planes_out=op if reads else None, planes_only=True)
+            return ops.conv2d(o, W(".conv2"), pad=1, residual=res, a_planes=op if reads else None)
+        o = ops.conv2d(x, W(".conv1"), pad=1, out_dtype=ctx.act, act=ACT_RELU, relu_in=True)
+        if not self.grouped:
+            res = skip()
+        return ops.conv2d(o, W(".conv2"), pad=1, out_dtype=ctx.act, residual=res)
 
     def _fusion(self, q, x0, x1):
-        ctx = self.ctx
+        """FeatureFusionBlock_custom.forward (dpt_block.py:198-237).  out_conv (1x1) commutes with the
+        align_corners=True bilinear x2 (both linear, weights sum to 1), so it runs at the low resolution."""
         out = x0 if x1 is None else self._rcu(q + ".resConfUnit1", x1, extra=x0)
         out = self._rcu(q + ".resConfUnit2", out)
-        B, G, hh, ww, Cc = out.shape
-        out = ops.linear_grouped(out.view(B, G, hh * ww, Cc), self._w("linear", q + ".out_conv"), out_dtype=ctx.act)
-        return ops.resize_bilinear(out.view(B * G, hh, ww, -1), (2 * hh, 2 * ww), True).view(B, G, 2 * hh, 2 * ww, -1)
+        lead, (hh, ww) = out.shape[:-3], out.shape[-3:-1]
+        out = ops.linear(out.flatten(-3, -2), self._w("linear", q + ".out_conv"), out_dtype=self.ctx.act)
+        return ops.resize_bilinear(out.view(-1, hh, ww, out.shape[-1]), (2 * hh, 2 * ww), True).view(*lead, 2 * hh, 2 * ww, -1)
 
     def trunk(self, tokens: Sequence[torch.Tensor], H, W):
-        """tokens: per hooked layer [B, 2, N, C] (strided view: both views' patch tokens)"""
+        """tokens: per hooked layer [*lead, N, C] fp32 (strided view: the patch tokens)"""
         ctx = self.ctx
         nh, nw = H // 16, W // 16
         layers = []
         for i, hk in enumerate(DPT_HOOKS):
             t = tokens[hk]
-            B, G = t.shape[:2]
             a = f".dpt.act_postprocess.{i}"
-            l = ops.linear_grouped(t, self._w("linear", a + ".0"), out_dtype=ctx.act).view(B, G, nh, nw, -1)
+            l = ops.linear(t, self._w("linear", a + ".0"), out_dtype=ctx.act).view(*t.shape[:-2], nh, nw, -1)
             if i in (0, 1):
-                l = ops.conv_transpose2d_grouped(l, self._w("convT", a + ".1"), out_dtype=ctx.act)
+                l = ops.conv_transpose2d(l, self._w("convT", a + ".1"), out_dtype=ctx.act)
             elif i == 3:
-                l = ops.conv2d_grouped(l, self._w("conv", a + ".1"), stride=2, pad=1, out_dtype=ctx.act)
-            layers.append(ops.conv2d_grouped(l, self._w("conv", f".dpt.scratch.layer_rn.{i}"), pad=1, out_dtype=ctx.act))
+                l = ops.conv2d(l, self._w("conv", a + ".1"), stride=2, pad=1, out_dtype=ctx.act)
+            layers.append(ops.conv2d(l, self._w("conv", f".dpt.scratch.layer_rn.{i}"), pad=1, out_dtype=ctx.act))
         s = ".dpt.scratch"
         path4 = self._fusion(s + ".refinenet4", layers[3], None)
         path3 = self._fusion(s + ".refinenet3", path4, layers[2])
         path2 = self._fusion(s + ".refinenet2", path3, layers[1])
         return self._fusion(s + ".refinenet1", path2, layers[0])
 
+    def _head4_names(self):
+        return tuple(q + ".dpt.head.4" for q in self.ps)
+
     def forward_pts3d(self, tokens, H, W):
-        """-> pts3d [B, 2, H, W, 3]"""
+        """PixelwiseTaskWithDPT.forward + postprocess 'exp' (dpt_head.py:113-120; postprocess.py:45-61) -> pts3d [*lead, H, W, 3]"""
         ctx = self.ctx
         x = self.trunk(tokens, H, W)
-        x = ops.conv2d_grouped(x, self._w("conv", ".dpt.head.0"), pad=1, out_dtype=ctx.act)
-        B, G = x.shape[:2]
-        x = ops.resize_bilinear(x.flatten(0, 1), (H, W), True).view(B, G, H, W, -1)
-        x = ops.conv2d_grouped(x, self._w("conv", ".dpt.head.2"), pad=1, out_dtype=ctx.act, act=ACT_RELU)
-        xyz = _head4(ctx, tuple(q + ".dpt.head.4" for q in self.ps), x.view(B, G, H * W, -1))
+        x = ops.conv2d(x, self._w("conv", ".dpt.head.0"), pad=1, out_dtype=ctx.act)
+        lead = x.shape[:-3]
+        x = ops.resize_bilinear(x.flatten(0, -4), (H, W), True).view(*lead, H, W, -1)
+        x = ops.conv2d(x, self._w("conv", ".dpt.head.2"), pad=1, out_dtype=ctx.act, act=ACT_RELU)
+        xyz = _head4(ctx, self._head4_names(), x.view(lead[0], len(self.ps), H * W, -1))
         if xyz is None:
-            xyz = ops.linear_grouped(x.view(B, G, H * W, -1), self._w("linear", ".dpt.head.4"), out_dtype=torch.float32)
-        return ops.pts3d_exp_(xyz).view(B, G, H, W, 3)
+            xyz = ops.linear(x.flatten(-3, -2), self._w("linear", ".dpt.head.4"), out_dtype=torch.float32)
+        return ops.pts3d_exp_(xyz).view(*lead, H, W, 3)
 
-    def forward_gs(self, tokens, img_nhwc8, H, W, out):
-        """img_nhwc8 [B, 2, H, W, c]; out: the model's [B, 2, H*W, 83] raw-Gaussian buffer (written in place)"""
+    def forward_gs(self, tokens, img, H, W, out=None):
+        """dpt_gs_head.py:121-171: feat_up(path_1) + ReLU(conv7x7(img)) fused into the stem's epilogue.  img [*lead, H, W, c] (the
+        packed image); out: optional [*lead, H*W, 83] fp32 destination (the model's raw-Gaussian buffer, or the views of it this head
+        serves; written in place).  Returns the raw Gaussians [*lead, H*W, 83]."""
         ctx = self.ctx
         path1 = self.trunk(tokens, H, W)
-        B, G = path1.shape[:2]
-        assert B == 1
-        x = torch.empty((B, G, H, W, path1.shape[-1]), dtype=ctx.act, device=ctx.dev)
-        w0 = self._w("conv", ".dpt.head.0")
-        # bf16x3: the stem's full-resolution map (268 MB per view) is read by head.0 only: pre-split planes when head.0's plan reads them
-        xp = ops.Planes(x, storage=x) if (ctx.split and _CONV_PLANES) else None
-        reads = xp is not None and bool(ops.conv2d_grouped(x, w0, pad=1, act=ACT_RELU, dry_run=True).a_x3_ok)
-        if _stem_kernel_ok(ctx, img_nhwc8, path1, H, W):  # both stems in ONE launch of the dedicated kernel (csrc/stem.hip)
+        lead, G = path1.shape[:-3], len(self.ps)
+        B = lead[0]
+        assert B == 1 or G == 1  # (the per-head slices below are contiguous)
+        # the stem's full-resolution map (268 MB per view in bf16x3) is read by head.0 only: pre-split planes when head.0's plan reads them
+        x = torch.empty((*lead, H, W, path1.shape[-1]), dtype=ctx.act, device=ctx.dev)
+        img5, up5, x5 = img.view(B, G, H, W, -1), path1.view(B, G, H // 2, W // 2, -1), x.view(B, G, H, W, -1)
+        head0 = lambda: self._w("conv", ".dpt.head.0")
+        stem = _stem_kernel_ok(ctx, img, path1, H, W)
+        if self.grouped or stem:  # (order only, as it was: a single head on the GEMM stem packs head.0 behind its stem)
+            head0()
+        xp = ops.Planes(x, storage=x) if (self._stem_gemm_planes() or (stem and self._stem_kernel_planes())) else None
+        reads = xp is not None and bool(ops.conv2d(x, head0(), pad=1, act=ACT_RELU, dry_run=True).a_x3_ok)
+        if stem:  # every stem in ONE launch of the dedicated kernel (csrc/stem.hip)
             wf, wb = ctx.w.stem7(tuple(q + ".dpt.input_merger.0" for q in self.ps))
-            reads = reads and not ops._NO_PRESPLIT
-            ops.stem7x7_x3(img_nhwc8, wf, wb, path1, x, planes=reads)
-            if reads:
-                xp.valid = xp.only = True
-            x = ops.conv2d_grouped(x, w0, pad=1, out_dtype=ctx.act, act=ACT_RELU, a_planes=xp if reads else None)
-            return self._gs_head4(x.view(B, G, H * W, -1), out)
-        wrote = []
-        for g, q in enumerate(self.ps):  # the stem: 7x7 image convolution + ReLU + x2 upsample-add of this head's path_1
-            xg = ops.Planes(x[:, g], storage=x[:, g]) if reads else None
-            ops.conv2d(img_nhwc8[:, g], ctx.w.conv(q + ".dpt.input_merger.0", cin_pad=ops.image_channels(ctx.split)), pad=3, act=ACT_RELU,
-                       up_src=path1[:, g], out=x[:, g], planes_out=xg, planes_only=True)  # (B == 1: the slices of a group are contiguous)
-            wrote.append(xg is not None and xg.valid)
-        if reads and any(wrote):
-            assert all(wrote), "the two stems of a pair run the same plan"
+            reads = reads and self._stem_kernel_planes()
+            ops.stem7x7_x3(img5, wf, wb, up5, x5, planes=reads)
+        else:
+            wrote = []
+            for g, q in enumerate(self.ps):  # the stem: 7x7 image convolution + ReLU + x2 upsample-add of this head's path_1
+                xg = ops.Planes(x5[:, g], storage=x5[:, g]) if reads else None
+                ops.conv2d(img5[:, g], ctx.w.conv(q + ".dpt.input_merger.0", cin_pad=ops.image_channels(ctx.split)), pad=3, act=ACT_RELU,
+                           up_src=up5[:, g], out=x5[:, g], planes_out=xg, planes_only=True)
+                wrote.append(xg is not None and xg.valid)
+            assert all(wrote) or not any(wrote), "the stems of a group run the same plan"
+            reads = reads and all(wrote)
+        if reads:
             xp.valid = xp.only = True
-        x = ops.conv2d_grouped(x, w0, pad=1, out_dtype=ctx.act, act=ACT_RELU, a_planes=xp if (reads and all(wrote)) else None)
-        return self._gs_head4(x.view(B, G, H * W, -1), out)
-
-    def _gs_head4(self, x, out):
-        """head.4 of both Gaussian heads into the model's raw-Gaussian buffer: the row-stream kernel (bf16x3, contiguous destination), else the grouped GEMM"""
-        r = _head4(self.ctx, tuple(q + ".dpt.head.4" for q in self.ps), x, out=out)
-        return r if r is not None else ops.linear_grouped(x, self._w("linear", ".dpt.head.4"), out=out)
+        x = ops.conv2d(x, head0(), pad=1, out_dtype=ctx.act, act=ACT_RELU, a_planes=xp if reads else None)
+        # head.4 into the destination: the row-stream kernel (bf16x3, dense rows), else the GEMM
+        if out is None:
+            out = torch.empty((*lead, H * W, ctx.w.sd[self.ps[0] + ".dpt.head.4.weight"].shape[0]), dtype=torch.float32, device=ctx.dev)
+        if _head4(ctx, self._head4_names(), x.view(B, G, H * W, -1), out=out if self.grouped else out.unsqueeze(1)) is None:
+            ops.linear(x.flatten(-3, -2), self._w("linear", ".dpt.head.4"), out=out)
+        return out
 
 
 class UnifiedGaussianAdapter:
@@ -1234,13 +1180,11 @@ class SIU3RModel:
         self.backbone = AsymmetricCroCo(self._ctx)
         self.adapter = CroCoViTAdapter(self._ctx, image_size)
         self.mask2former = VideoMask2FormerForVideoSegmentation(self._ctx, num_queries)
-        self.downstream_head1 = _DPTHead(self._ctx, "downstream_head1", gs=False)
-        self.downstream_head2 = _DPTHead(self._ctx, "downstream_head2", gs=False)
-        self.gaussian_param_head1 = _DPTHead(self._ctx, "gaussian_param_head1", gs=True)
-        self.gaussian_param_head2 = _DPTHead(self._ctx, "gaussian_param_head2", gs=True)
+        pts, gs = ("downstream_head1", "downstream_head2"), ("gaussian_param_head1", "gaussian_param_head2")
+        self.downstream_head1, self.downstream_head2 = (_DPTHeads(self._ctx, (q,), gs=False) for q in pts)
+        self.gaussian_param_head1, self.gaussian_param_head2 = (_DPTHeads(self._ctx, (q,), gs=True) for q in gs)
         # the two heads of a kind as one sequence of grouped launches (one pair, one item: the benchmarked shape)
-        self.gs_pair = _DPTHeadPair(self._ctx, ("gaussian_param_head1", "gaussian_param_head2"), gs=True)
-        self.pts_pair = _DPTHeadPair(self._ctx, ("downstream_head1", "downstream_head2"), gs=False)
+        self.gs_pair, self.pts_pair = _DPTHeads(self._ctx, gs, gs=True), _DPTHeads(self._ctx, pts, gs=False)
         self.gaussian_adapter = UnifiedGaussianAdapter(sh_degree=sh_degree)
         self.processor = pp.VideoMask2FormerImageProcessor()
         self.raw_gs_dim = (sh_degree + 1) ** 2 * 3 + 3 + 4 + 1
@@ -1480,10 +1424,10 @@ class SIU3RModel:
         for k in range(len(ADAPTER_IDX)):
             enc += [(f"enc{k}", lambda k=k: enc_seg(k)), (f"int{k}", lambda k=k: interact(k))]
         if self._paired_heads(st):
-            heads = [("gs", lambda: self._s_head_pair(st, True)), ("pts", lambda: self._s_head_pair(st, False))]
+            heads = [("gs", lambda: self._s_head(st, True)), ("pts", lambda: self._s_head(st, False))]
         else:
-            heads = [("gs0", lambda: self._s_head(st, 0)), ("gsr", lambda: self._s_head(st, 1)), ("pts0", lambda: self._s_head(st, 2)),
-                     ("ptsr", lambda: self._s_head(st, 3))]
+            heads = [("gs0", lambda: self._s_head(st, True, 0)), ("gsr", lambda: self._s_head(st, True, 1)), ("pts0", lambda: self._s_head(st, False, 0)),
+                     ("ptsr", lambda: self._s_head(st, False, 1))]
         return enc + [("seg", lambda: self._s_seg(st))] + dec + heads + [("tail", lambda: self._s_tail(st))]
 
     def _paired_heads(self, st) -> bool:
@@ -1611,33 +1555,26 @@ class SIU3RModel:
         r = t[:, 1:]
         return r[0] if t.shape[0] == 1 else (r[:, 0] if t.shape[1] == 2 else r.reshape(-1, *t.shape[2:]))
 
-    def _s_head(self, st, i):
-        """i = 0: GS head of view 0 (gaussian_param_head1), 1: GS head of views 1.. (head2), 2 / 3: the pts3d heads."""
+    def _s_head(self, st, gs: bool, side=None):
+        """One chain of DPT heads, Gaussian (gs) or pts3d.  side 0: head1 on view 0; side 1: head2 on the views 1.. as one batch; side None:
+        both heads of a kind (view 0 -> head1, view 1 -> head2) as grouped launches."""
         B, V, _, H, W = st.images.shape
-        first = i in (0, 2)
-        toks = [(t[:, 0] if first else self._rest_views(t))[..., :-1, :] for t in st.dec["layers"]]
-        if i < 2:
-            img8 = st.img8.view(B, V, H, W, st.img8.shape[-1])
-            img = (img8[:, 0] if first else self._rest_views(img8)).contiguous()
-            head = self.gaussian_param_head1 if first else self.gaussian_param_head2
-            # the last GEMM writes straight into the [B, V, H*W, 83] buffer the Gaussian adapter reads (no 350 MB concat),
-            # whenever this head's views form one strided batch of it
-            dst = st.raw[:, 0] if first else (st.raw[:, 1] if V == 2 else (st.raw[0, 1:] if B == 1 else None))
-            st.gs[0 if first else 1] = head.forward_gs(toks, img, H, W, out=dst)
-        else:
-            head = self.downstream_head1 if first else self.downstream_head2
-            st.pts[0 if first else 1] = head.forward_pts3d(toks, H, W)["pts3d"]
-
-    def _s_head_pair(self, st, gs: bool):
-        """both heads of a kind (view 0 -> head1, view 1 -> head2) as grouped launches"""
-        B, V, _, H, W = st.images.shape
-        toks = [t[..., :-1, :] for t in st.dec["layers"]]  # [B, 2, N, C]: the patch tokens of both views
+        views = (lambda t: t) if side is None else (lambda t: t[:, 0]) if side == 0 else self._rest_views
+        toks = [views(t)[..., :-1, :] for t in st.dec["layers"]]  # the patch tokens
+        heads = (self.gs_pair, self.gaussian_param_head1, self.gaussian_param_head2) if gs else (self.pts_pair, self.downstream_head1, self.downstream_head2)
+        head = heads[0 if side is None else 1 + side]
         if gs:
-            self.gs_pair.forward_gs(toks, st.img8.view(B, V, H, W, st.img8.shape[-1]), H, W, out=st.raw)
-            st.gs = [st.raw[:, 0], st.raw[:, 1]]
+            # the last GEMM writes straight into the [B, V, H*W, 83] buffer the Gaussian adapter reads (no 350 MB concat),
+            # whenever this chain's views form one strided batch of it
+            dst = st.raw if side is None else st.raw[:, side] if (side == 0 or V == 2) else (st.raw[0, 1:] if B == 1 else None)
+            r = head.forward_gs(toks, views(st.img8.view(B, V, H, W, -1)).contiguous(), H, W, out=dst)
         else:
-            pts = self.pts_pair.forward_pts3d(toks, H, W)
-            st.pts = [pts[:, 0], pts[:, 1]]
+            r = head.forward_pts3d(toks, H, W)
+        res = st.gs if gs else st.pts
+        if side is None:
+            res[:] = [r[:, 0], r[:, 1]]
+        else:
+            res[side] = r
 
     def _s_tail(self, st):
         B, V, _, H, W = st.images.shape

@@ -173,25 +173,21 @@ class KernelTimer:
     def __init__(self):
         self.records = []  # (variant, flops, ev0, ev1, shape)
 
-    def summary(self):
+    def _totals(self, key):
         torch.cuda.synchronize()
         out = {}
-        for variant, fl, e0, e1, _ in self.records:
-            d = out.setdefault(variant, dict(launches=0, flops=0.0, ms=0.0))
+        for variant, fl, e0, e1, shape in self.records:
+            d = out.setdefault(key(variant, shape), dict(launches=0, flops=0.0, ms=0.0))
             d["launches"] += 1
             d["flops"] += fl
             d["ms"] += e0.elapsed_time(e1)
         return out
 
+    def summary(self):
+        return self._totals(lambda variant, shape: variant)
+
     def by_shape(self):
-        torch.cuda.synchronize()
-        out = {}
-        for variant, fl, e0, e1, shape in self.records:
-            d = out.setdefault((variant,) + shape, dict(launches=0, flops=0.0, ms=0.0))
-            d["launches"] += 1
-            d["flops"] += fl
-            d["ms"] += e0.elapsed_time(e1)
-        return out
+        return self._totals(lambda variant, shape: (variant,) + shape)
 
 
 _timer: Optional[KernelTimer] = None
@@ -409,6 +405,18 @@ def _apply_ln_stats_aux(p: GemmParams, pw: PackedWeight, x, out, lda, ldc, strid
         p.c_aux = _p(aux_out)
 
 
+def _apply_rope(p: GemmParams, rope, rows: int):
+    """rope = (cos, sin, positions int64 [rows, 2] contiguous, ncols): fused RoPE2D on output columns [0, ncols)"""
+    cos, sin, pos, ncols = rope
+    assert pos.dtype == torch.int64 and pos.is_contiguous() and pos.numel() == 2 * rows and cos.shape[1] == 16
+    p.rope_cos, p.rope_sin, p.rope_pos, p.rope_ncols = _p(cos), _p(sin), _p(pos), ncols
+
+
+def _groups(pw: PackedWeight) -> int:
+    """G of a stack_packed weight, 0 for a plain one"""
+    return (pw.meta or {}).get("groups", 0)
+
+
 def linear(x: torch.Tensor, pw: PackedWeight, *, out_dtype=torch.float32, act=ACT_NONE,
            residual: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, relu_in=False,
            rope=None, ln: Optional[RowStats] = None, stats_out: Optional[RowStats] = None, aux_out: Optional[torch.Tensor] = None,
@@ -424,7 +432,13 @@ def linear(x: torch.Tensor, pw: PackedWeight, *, out_dtype=torch.float32, act=AC
     planes_out: Planes of the output, written when the plan can (planes_out.valid says so afterwards); planes_only: then do NOT write the
     fp32 output (`out` stays untouched; planes_out.only = True).  dry_run: launch nothing, return the siu3r_gemm_plan_t of the launch as it
     would be issued with fp32 A (its a_x3_ok / c_x3_ok tell whether planes could be consumed / emitted).  planes_from_col (with
-    planes_out whose storage IS `out`): a mixed output -- fp32 in columns [0, planes_from_col), planes behind them."""
+    planes_out whose storage IS `out`): a mixed output -- fp32 in columns [0, planes_from_col), planes behind them.
+    A stacked weight (stack_packed) makes this linear_grouped(x [B, G, M, K], ...), which has the arguments it names."""
+    if _groups(pw):
+        if relu_in or splitk or planes_only or dry_run or a_planes is not None:
+            raise RuntimeError("relu_in / splitk / a_planes / planes_only / dry_run are not available with a stacked weight (linear_grouped)")
+        return linear_grouped(x, pw, out_dtype=out_dtype, act=act, residual=residual, out=out, rope=rope, ln=ln, stats_out=stats_out, aux_out=aux_out,
+                              planes_out=planes_out, planes_from_col=planes_from_col)
     _gpu(x, residual, out)
     assert x.shape[-1] == pw.k, (x.shape, pw.k)
     if out is None:
@@ -454,11 +468,14 @@ def linear(x: torch.Tensor, pw: PackedWeight, *, out_dtype=torch.float32, act=AC
         p.batch, p.sa, p.sw, p.sc = Z, bsa, 0, bsc
         p.sr = bs(zr, mr, ldr, sr) if residual is not None else 0
     if rope is not None:
-        cos, sin, pos, ncols = rope
-        assert pos.dtype == torch.int64 and pos.is_contiguous() and pos.numel() == 2 * total and cos.shape[1] == 16
-        p.rope_cos, p.rope_sin, p.rope_pos, p.rope_ncols = _p(cos), _p(sin), _p(pos), ncols
+        _apply_rope(p, rope, total)
     _apply_ln_stats_aux(p, pw, x, out, lda, ldc, (bsa, 0, bsc, 0), ln, stats_out, aux_out)
     p.splitk = splitk
+    return _launch(p, x, out, a_planes, planes_out, planes_only, dry_run, planes_from_col)
+
+
+def _launch(p: GemmParams, x, out, a_planes=None, planes_out=None, planes_only=False, dry_run=False, planes_from_col=0):
+    """the tail of a GEMM wrapper: the pre-split operands it was asked for (see linear()), then the launch -> out; dry_run: the plan, no launch"""
     if dry_run or a_planes is not None or planes_out is not None:
         p.c_x3_col0 = planes_from_col
         pl = _apply_planes(p, x, out, a_planes, planes_out, planes_only and planes_from_col == 0, dry_run)
@@ -522,15 +539,9 @@ def linear_grouped(x: torch.Tensor, pw: PackedWeight, *, out_dtype=torch.float32
         assert residual.shape == out.shape and residual.stride(3) == 1
         p.ldr, p.sr, p.sr_i = residual.stride(2), residual.stride(0), residual.stride(1)
     if rope is not None:
-        cos, sin, pos, ncols = rope
-        assert pos.dtype == torch.int64 and pos.is_contiguous() and pos.numel() == 2 * B * G * M and cos.shape[1] == 16
-        p.rope_cos, p.rope_sin, p.rope_pos, p.rope_ncols = _p(cos), _p(sin), _p(pos), ncols
+        _apply_rope(p, rope, B * G * M)
     _apply_ln_stats_aux(p, pw, x, out, p.lda, p.ldc, (p.sa, sa_i, p.sc, p.sc_i), ln, stats_out, aux_out, x_first=xf)
-    if planes_out is not None:
-        p.c_x3_col0 = planes_from_col
-        _apply_planes(p, x, out, None, planes_out, False, False)
-    _gemm_launch(p)
-    return out
+    return _launch(p, x, out, planes_out=planes_out, planes_from_col=planes_from_col)
 
 
 def bmm_nt(a: torch.Tensor, b_hi: torch.Tensor, b_lo: Optional[torch.Tensor], n: int, k: int, *, out_dtype=torch.float32,
@@ -552,59 +563,6 @@ def bmm_nt(a: torch.Tensor, b_hi: torch.Tensor, b_lo: Optional[torch.Tensor], n:
     return out
 
 
-def conv2d(x: torch.Tensor, pw: PackedWeight, *, stride=1, pad=0, out_dtype=torch.float32, act=ACT_NONE,
-           residual=None, relu_in=False, up_src: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
-           a_planes: Optional[Planes] = None, planes_out: Optional[Planes] = None, planes_only: bool = False, dry_run: bool = False):
-    """NHWC implicit-GEMM convolution: x [B, IH, IW, Cin] -> [B, OH, OW, Cout] (out: optional contiguous destination).
-    a_planes / planes_out / planes_only / dry_run: pre-split bf16x3 operands, as in linear()."""
-    _gpu(x, residual, up_src, out)
-    assert x.is_contiguous()
-    B, IH, IW, Cin = x.shape
-    kh, kw = pw.meta["kh"], pw.meta["kw"]
-    assert Cin == pw.meta["cin"], (Cin, pw.meta)
-    OH = (IH + 2 * pad - kh) // stride + 1
-    OW = (IW + 2 * pad - kw) // stride + 1
-    if out is None:
-        out = torch.empty((B, OH, OW, pw.n), dtype=out_dtype, device=x.device)
-    assert out.shape == (B, OH, OW, pw.n) and out.is_contiguous()
-    p = GemmParams()
-    _fill_common(p, x, pw, out, act, residual, relu_in)
-    p.m, p.ldc, p.ldr = B * OH * OW, pw.n, pw.n
-    p.a_mode = 1
-    p.ih, p.iw, p.cin, p.kh, p.kw, p.stride, p.pad, p.oh, p.ow = IH, IW, Cin, kh, kw, stride, pad, OH, OW
-    if up_src is not None:
-        assert up_src.is_contiguous() and up_src.shape == (B, OH // 2, OW // 2, pw.n)
-        p.up_src, p.up_dtype = _p(up_src), _dt(up_src)
-    if dry_run or a_planes is not None or planes_out is not None:
-        pl = _apply_planes(p, x, out, a_planes, planes_out, planes_only, dry_run)
-        if dry_run:
-            return pl
-    _gemm_launch(p)
-    return out
-
-
-def conv_transpose2d(x: torch.Tensor, pw: PackedWeight, *, out_dtype=torch.float32, residual=None):
-    """ConvTranspose2d with kernel == stride (pixel shuffle epilogue): [B,IH,IW,Cin] -> [B,IH*up,IW*up,Cout].  x may be a view whose
-    batch items are dense but lie further apart: each item is then one batch of the launch (blockIdx.z)."""
-    _gpu(x, residual)
-    B, IH, IW, Cin = x.shape
-    x_bs = _batch_strided(x, IH * IW * Cin)
-    up, cout = pw.meta["up"], pw.meta["cout"]
-    out = torch.empty((B, IH * up, IW * up, cout), dtype=out_dtype, device=x.device)
-    p = GemmParams()
-    _fill_common(p, x, pw, out, ACT_NONE, residual, False)
-    p.out_mode, p.up, p.cout, p.ih, p.iw = 1, up, cout, IH, IW
-    if B == 1 or x_bs == IH * IW * Cin:
-        p.m, p.lda = B * IH * IW, Cin
-    else:
-        assert residual is None or residual.is_contiguous()
-        p.m, p.lda = IH * IW, Cin
-        p.batch, p.sa, p.sw, p.sc = B, x_bs, 0, out[0].numel()
-        p.sr = out[0].numel() if residual is not None else 0
-    _gemm_launch(p)
-    return out
-
-
 def _grouped_common(p: GemmParams, x, pw: PackedWeight, out, residual):
     """two-level batching of a grouped launch over images [B, G, ...]: blockIdx.z = b * G + g, weight set g"""
     G = pw.meta["groups"]
@@ -619,48 +577,74 @@ def _grouped_common(p: GemmParams, x, pw: PackedWeight, out, residual):
         p.sr, p.sr_i = residual.stride(0), residual.stride(1)
 
 
-def conv2d_grouped(x: torch.Tensor, pw: PackedWeight, *, stride=1, pad=0, out_dtype=torch.float32, act=ACT_NONE, residual=None, relu_in=False,
-                   out: Optional[torch.Tensor] = None, a_planes: Optional[Planes] = None, planes_out: Optional[Planes] = None, planes_only: bool = False,
-                   dry_run: bool = False):
-    """conv2d for G networks of the same shape in ONE launch: x [B, G, IH, IW, Cin] -> [B, G, OH, OW, Cout], image (b, g) convolved with
-    weight set g of pw = stack_packed([...G sets]) (the two DPT heads of a kind: head1 on view 0, head2 on view 1 -- reference
-    model.py:352-375 runs them one after the other)."""
-    _gpu(x, residual)
-    B, G, IH, IW, Cin = x.shape
+def _image_dims(x: torch.Tensor, pw: PackedWeight):
+    """x [B, IH, IW, Cin] with a plain weight, [B, G, IH, IW, Cin] with pw = stack_packed([...G sets]) -> (G or 0, leading shape, IH, IW, Cin)"""
+    G = _groups(pw)
+    if x.dim() != (5 if G else 4) or (G and x.shape[1] != G):
+        want = f"[B, {G}, IH, IW, Cin] (a stacked weight of {G} sets)" if G else "[B, IH, IW, Cin] (a plain weight)"
+        raise RuntimeError(f"x must be {want}, got {tuple(x.shape)}")
+    return G, tuple(x.shape[:-3]), x.shape[-3], x.shape[-2], x.shape[-1]
+
+
+def conv2d(x: torch.Tensor, pw: PackedWeight, *, stride=1, pad=0, out_dtype=torch.float32, act=ACT_NONE,
+           residual=None, relu_in=False, up_src: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+           a_planes: Optional[Planes] = None, planes_out: Optional[Planes] = None, planes_only: bool = False, dry_run: bool = False):
+    """NHWC implicit-GEMM convolution: x [B, IH, IW, Cin] -> [B, OH, OW, Cout] (out: optional contiguous destination).  With
+    pw = stack_packed([...G sets]): G networks of the same shape in ONE launch, x [B, G, IH, IW, Cin] -> [B, G, OH, OW, Cout], image (b, g)
+    convolved with weight set g (the two DPT heads of a kind: head1 on view 0, head2 on view 1 -- reference model.py:352-375 runs them
+    one after the other).  up_src (the x2 upsample-add epilogue) is for a plain weight only.
+    a_planes / planes_out / planes_only / dry_run: pre-split bf16x3 operands, as in linear()."""
+    _gpu(x, residual, up_src, out)
+    G, lead, IH, IW, Cin = _image_dims(x, pw)
+    if G and up_src is not None:
+        raise RuntimeError("conv2d: up_src is not available with a stacked weight (run one plain convolution per weight set)")
+    assert x.is_contiguous()
     kh, kw = pw.meta["kh"], pw.meta["kw"]
     assert Cin == pw.meta["cin"], (Cin, pw.meta)
     OH = (IH + 2 * pad - kh) // stride + 1
     OW = (IW + 2 * pad - kw) // stride + 1
     if out is None:
-        out = torch.empty((B, G, OH, OW, pw.n), dtype=out_dtype, device=x.device)
-    assert out.shape == (B, G, OH, OW, pw.n) and out.is_contiguous()
+        out = torch.empty((*lead, OH, OW, pw.n), dtype=out_dtype, device=x.device)
+    assert out.shape == (*lead, OH, OW, pw.n) and out.is_contiguous()
     p = GemmParams()
     _fill_common(p, x, pw, out, act, residual, relu_in)
-    p.m, p.ldc, p.ldr = OH * OW, pw.n, pw.n
+    p.m, p.ldc, p.ldr = (OH * OW if G else lead[0] * OH * OW), pw.n, pw.n
     p.a_mode = 1
     p.ih, p.iw, p.cin, p.kh, p.kw, p.stride, p.pad, p.oh, p.ow = IH, IW, Cin, kh, kw, stride, pad, OH, OW
-    _grouped_common(p, x, pw, out, residual)
-    if dry_run or a_planes is not None or planes_out is not None:  # pre-split bf16x3 operands, as in linear()
-        pl = _apply_planes(p, x, out, a_planes, planes_out, planes_only, dry_run)
-        if dry_run:
-            return pl
-    _gemm_launch(p)
-    return out
+    if G:
+        _grouped_common(p, x, pw, out, residual)
+    if up_src is not None:
+        assert up_src.is_contiguous() and up_src.shape == (*lead, OH // 2, OW // 2, pw.n)
+        p.up_src, p.up_dtype = _p(up_src), _dt(up_src)
+    return _launch(p, x, out, a_planes, planes_out, planes_only, dry_run)
 
 
-def conv_transpose2d_grouped(x: torch.Tensor, pw: PackedWeight, *, out_dtype=torch.float32):
-    """conv_transpose2d (kernel == stride) for G weight sets in one launch: x [B, G, IH, IW, Cin] -> [B, G, IH*up, IW*up, Cout]"""
-    _gpu(x)
-    B, G, IH, IW, Cin = x.shape
+def conv_transpose2d(x: torch.Tensor, pw: PackedWeight, *, out_dtype=torch.float32, residual=None):
+    """ConvTranspose2d with kernel == stride (pixel shuffle epilogue): [B,IH,IW,Cin] -> [B,IH*up,IW*up,Cout].  x may be a view whose
+    batch items are dense but lie further apart: each item is then one batch of the launch (blockIdx.z).  With pw = stack_packed([...G
+    sets]): x [B, G, IH, IW, Cin] contiguous -> [B, G, IH*up, IW*up, Cout] in one launch (no residual)."""
+    _gpu(x, residual)
+    G, lead, IH, IW, Cin = _image_dims(x, pw)
+    if G and residual is not None:
+        raise RuntimeError("conv_transpose2d: residual is not available with a stacked weight")
+    B = lead[0]
     up, cout = pw.meta["up"], pw.meta["cout"]
-    out = torch.empty((B, G, IH * up, IW * up, cout), dtype=out_dtype, device=x.device)
+    out = torch.empty((*lead, IH * up, IW * up, cout), dtype=out_dtype, device=x.device)
     p = GemmParams()
-    _fill_common(p, x, pw, out, ACT_NONE, None, False)
+    _fill_common(p, x, pw, out, ACT_NONE, residual, False)
     p.out_mode, p.up, p.cout, p.ih, p.iw = 1, up, cout, IH, IW
     p.m, p.lda = IH * IW, Cin
-    _grouped_common(p, x, pw, out, None)
-    _gemm_launch(p)
-    return out
+    if G:
+        _grouped_common(p, x, pw, out, None)
+    else:
+        x_bs = _batch_strided(x, IH * IW * Cin)
+        if B == 1 or x_bs == IH * IW * Cin:
+            p.m = B * IH * IW
+        else:  # one batch of the launch per item
+            assert residual is None or residual.is_contiguous()
+            p.batch, p.sa, p.sw, p.sc = B, x_bs, 0, out[0].numel()
+            p.sr = out[0].numel() if residual is not None else 0
+    return _launch(p, x, out)
 
 
 def patch_embed(img: torch.Tensor, pw: PackedWeight, out: torch.Tensor, stats_out: Optional[RowStats] = None, aux_out: Optional[torch.Tensor] = None):
@@ -680,20 +664,14 @@ def patch_embed(img: torch.Tensor, pw: PackedWeight, out: torch.Tensor, stats_ou
     else:  # extra tokens per batch item: one launch per batch via blockIdx.z
         p.m, p.ldc = h * w, out.stride(1)
         p.batch, p.sa, p.sw, p.sc = B, 3 * H * W, 0, out.stride(0)
-    if stats_out is not None:
-        p.stats_out = stats_out.ptr(stats_out.row_of(out))
-        p.st_ldm, p.st_sz = stats_out.div(p.ldc), (stats_out.div(p.sc) if p.batch > 1 else 0)
-    if aux_out is not None:
-        assert aux_out.dtype == torch.bfloat16 and aux_out.shape == out.shape and aux_out.stride() == out.stride()
-        p.c_aux = _p(aux_out)
-    _gemm_launch(p)
-    return out
+    _apply_ln_stats_aux(p, pw, img, out, 0, p.ldc, (0, 0, p.sc, 0), None, stats_out, aux_out)
+    return _launch(p, img, out)
 
 
 # ------------------------------------------------------------------------------------------------
 # attention / norms / element-wise
 # ------------------------------------------------------------------------------------------------
-_ATTN_SPLITKV = __import__("os").environ.get("SIU3R_NO_ATTN_SPLITKV", "0") != "1"
+_ATTN_SPLITKV = os.environ.get("SIU3R_NO_ATTN_SPLITKV", "0") != "1"
 
 
 def attention(q, k, v, *, heads: int, head_dim: int, scale: float, rope=None, qpos=None, kpos=None,

@@ -305,6 +305,54 @@ def test_conv_transpose(mode, k):
     check(f"conv_transpose[{name}] k{k}", out, ref, tol)
 
 
+@pytest.mark.parametrize("mode", MODES, ids=[m[0] for m in MODES])
+@pytest.mark.parametrize("cfg", [(3, 1, 1, 16, 24, True), (3, 2, 1, 96, 72, False)], ids=["k3s1_relu_in_residual", "k3s2c96_ring"])
+def test_conv2d_grouped(mode, cfg):
+    """conv2d with a stacked weight (ops.stack_packed): x [B, G, IH, IW, Cin], image (b, g) convolved with weight set g in ONE launch --
+    each image against F.conv2d with its group's weights; the shapes a stacked weight does not serve are refused."""
+    ops = _ops()
+    name, adt, split, tol = mode
+    k, s, pd, cin, cout, fused = cfg  # fused: ReLU on the input and a residual in the epilogue
+    B, G, H, W = 2, 2, 20, 28
+    x = gen(B, G, cin, H, W, seed=30)
+    w, b = gen(G, cout, cin, k, k, seed=31, scale=0.3), gen(G, cout, seed=32)
+    OH, OW = (H + 2 * pd - k) // s + 1, (W + 2 * pd - k) // s + 1
+    r = gen(B, G, OH, OW, cout, seed=33)
+    pw = ops.stack_packed([ops.pack_conv(w[g].cuda(), b[g].cuda(), split) for g in range(G)])
+    xg = x.permute(0, 1, 3, 4, 2).contiguous().cuda().to(adt)
+    out = ops.conv2d(xg, pw, stride=s, pad=pd, out_dtype=torch.float32, relu_in=fused, residual=r.cuda().to(adt) if fused else None)
+    assert out.shape == (B, G, OH, OW, cout)
+    for i in range(B):
+        for g in range(G):
+            xi = x[i, g].to(adt).float()[None]
+            ref = F.conv2d(F.relu(xi) if fused else xi, w[g], b[g], stride=s, padding=pd).permute(0, 2, 3, 1)[0]
+            if fused:
+                ref = ref + r[i, g].to(adt).float()
+            check(f"conv2d_grouped[{name}] k{k}s{s} image ({i}, {g})", out[i, g], ref, tol)
+    with pytest.raises(RuntimeError, match="stacked weight"):
+        ops.conv2d(xg[:, 0], pw, stride=s, pad=pd)
+    with pytest.raises(RuntimeError, match="up_src"):
+        ops.conv2d(xg, pw, stride=s, pad=pd, up_src=torch.zeros(B, G, OH // 2, OW // 2, cout, device="cuda", dtype=adt))
+
+
+@pytest.mark.parametrize("mode", MODES, ids=[m[0] for m in MODES])
+@pytest.mark.parametrize("k", [2, 4])
+def test_conv_transpose_grouped(mode, k):
+    """conv_transpose2d with a stacked weight: x [B, G, IH, IW, Cin] -> [B, G, IH*k, IW*k, Cout], image (b, g) with weight set g"""
+    ops = _ops()
+    name, adt, split, tol = mode
+    B, G, H, W, cin, cout = 2, 2, 6, 5, 48, 24
+    x = gen(B, G, cin, H, W, seed=34)
+    w, b = gen(G, cin, cout, k, k, seed=35, scale=0.3), gen(G, cout, seed=36)
+    pw = ops.stack_packed([ops.pack_conv_transpose(w[g].cuda(), b[g].cuda(), split) for g in range(G)])
+    out = ops.conv_transpose2d(x.permute(0, 1, 3, 4, 2).contiguous().cuda().to(adt), pw, out_dtype=torch.float32)
+    assert out.shape == (B, G, H * k, W * k, cout)
+    for i in range(B):
+        for g in range(G):
+            ref = F.conv_transpose2d(x[i, g].to(adt).float()[None], w[g], b[g], stride=k).permute(0, 2, 3, 1)[0]
+            check(f"conv_transpose_grouped[{name}] k{k} image ({i}, {g})", out[i, g], ref, tol)
+
+
 @pytest.mark.parametrize("split", [False, True], ids=["bf16", "bf16x3"])
 def test_patch_embed(split):
     ops = _ops()
@@ -1129,6 +1177,41 @@ def test_gemm_presplit_planes(cfg):
         xq = ops.Planes(x1)
         ops.linear(a, pw, residual=r, out=x1, planes_out=xq)  # the 128 x 64 family: no planes, and the caller is told so
         assert not xq.valid
+    finally:
+        ops.set_plan_log(None)
+        ops.gemm_tune(0, 0)
+
+
+@pytest.mark.parametrize("cfg", [1, 2, 3])
+def test_conv2d_grouped_presplit_planes(cfg):
+    """The convolution part of test_gemm_presplit_planes as ONE grouped launch per convolution (what the residual units of the paired DPT
+    heads run): its two images as groups [1, 2, 24, 40, 64] with a weight set each.  The plan of the second convolution reads planes at
+    this size (24 x 40: a_x3_ok == 1 under every ping-pong tile), the planes-only producer leaves the hi / lo bit patterns of the fp32
+    launch's output, and the consumer on planes returns the bits of the consumer on the fp32 operand."""
+    ops = _ops()
+    ops.gemm_tune(0, cfg)
+    try:
+        xin = gen(2, 24, 40, 64, seed=220).cuda().view(1, 2, 24, 40, 64)
+        c1 = ops.stack_packed([ops.pack_conv(gen(64, 64, 3, 3, seed=221 + 10 * g, scale=0.1).cuda(), gen(64, seed=222 + 10 * g).cuda(), True) for g in range(2)])
+        c2 = ops.stack_packed([ops.pack_conv(gen(128, 64, 3, 3, seed=223 + 10 * g, scale=0.1).cuda(), gen(128, seed=224 + 10 * g).cuda(), True) for g in range(2)])
+        o_ref = ops.conv2d(xin, c1, pad=1, act=ops.ACT_RELU, relu_in=True)
+        y_ref = ops.conv2d(o_ref, c2, pad=1)
+        o = torch.empty_like(o_ref)
+        op = ops.Planes(o, storage=o)
+        pl = ops.conv2d(o, c2, pad=1, dry_run=True)
+        assert pl.a_x3_ok == 1 and pl.tile_cfg == cfg, (pl.a_x3_ok, pl.tile_cfg)
+        ops.conv2d(xin, c1, pad=1, act=ops.ACT_RELU, relu_in=True, out=o, planes_out=op, planes_only=True)
+        assert op.valid and op.only and torch.equal(o.view(-1, 64).cpu().contiguous().view(torch.int16), _planes_reference(o_ref.view(-1, 64)))
+        log = []
+        ops.set_plan_log(log)
+        yc = ops.conv2d(o, c2, pad=1, a_planes=op)
+        ops.set_plan_log(None)
+        assert log[-1].kernel.count(b",") == 6 and b", 1, false, false, true>" in log[-1].kernel, log[-1].kernel  # the pre-split instantiation ran
+        assert torch.equal(yc, y_ref), f"grouped convolution on planes: max diff {(yc - y_ref).abs().max().item():.3e}"
+        # the groups really use their own weights: group g against the plain launch of image g with weight set g
+        for g in range(2):
+            w, b = gen(128, 64, 3, 3, seed=223 + 10 * g, scale=0.1), gen(128, seed=224 + 10 * g)
+            check(f"grouped planes[{cfg}] group {g} vs torch", yc[0, g], F.conv2d(o_ref[0, g].cpu().permute(2, 0, 1)[None], w, b, padding=1)[0].permute(1, 2, 0), TOL_F32)
     finally:
         ops.set_plan_log(None)
         ops.gemm_tune(0, 0)
