@@ -587,6 +587,45 @@ int64_t siu3r_gaussian_adam_ws(int64_t G);
 int siu3r_gaussian_adam(const siu3r_adam_field* fields, int n_fields, int64_t G, double beta1, double beta2, float eps, float bc1, float bc2,
                         const int32_t* radii, int V, int R, const uint8_t* mask, void* ws, void* stream);
 
+/* ---- MCMC densification of splat refinement (csrc/mcmc.hip; Kheradmand et al. 2024): relocate, grow, noise ----
+ * All parameters are the UNCONSTRAINED ones of the refinement loop, fp32, contiguous, on the device: means [G,3], log-scales [G,3], raw
+ * (x, y, z, w) quaternions [G,4], logit opacities [G].  1 <= G <= 2^30.  Deterministic (no float atomics; two calls on equal inputs give
+ * equal bits), nothing allocates or synchronises with the host.  ws: siu3r_mcmc_ws(G) BYTES of workspace, 8-byte aligned.
+ * Weights.  w[g] = (uint32) rint(sigmoid(a[g]) * 2^24), the sigmoid in fp64 (a NaN gives 0);  dead[g] = a[g] <= logit_min_opacity, an fp32
+ * comparison.  relocate != 0: a dead row gets w = 0 (it is never drawn); relocate == 0 (growth): every row keeps its weight. */
+int64_t siu3r_mcmc_ws(int64_t G);
+int siu3r_mcmc_weights(const float* logit_opacity, int64_t G, float logit_min_opacity, int relocate, uint32_t* w, uint8_t* dead, void* stream);
+/* Scan.  cum [G] = the inclusive scan of w in uint64 (total = cum[G - 1] < 2^54 for weights up to 2^24).  dead (or NULL: dead_idx and n_dead
+ * are then not touched): dead_idx [G] receives the indices of the dead rows in memory order, n_dead (device) their number. */
+int siu3r_mcmc_scan(const uint32_t* w, const uint8_t* dead, int64_t G, uint64_t* cum, int32_t* dead_idx, int32_t* n_dead, void* ws, void* stream);
+/* Draws.  rbits [n] int64: the caller's random words, of which the low 32 bits r are used.  t = (r * total) >> 32, exact (the product has up
+ * to 86 bits);  sampled[j] = the smallest g with cum[g] > t;  count [G] = how many of the n draws chose each row (cleared here).  All
+ * integer: a pure function of (cum, rbits).  total == 0 (no row has a weight) makes every draw row 0.  0 <= n <= 2^32. */
+int siu3r_mcmc_sample(const uint64_t* cum, int64_t G, const int64_t* rbits, int64_t n, int32_t* sampled, int32_t* count, void* stream);
+/* Relocation update, in place, of every row with count[g] > 0, the row evaluated in fp64 and rounded once per output:
+ *   N = min(count[g] + 1, 51);  o = sigmoid(a[g]);  o_new = 1 - (1 - o)^(1 / N);
+ *   denom = sum_{i=1..N} sum_{k=0..i-1} C(i-1, k) (-1)^k o_new^(k+1) / sqrt(k+1)   (summed over i first: sum_i C(i-1, k) = C(N, k+1));
+ *   log_scales[g,:] += log(o / denom);  a[g] = logit(clamp(o_new, min_opacity, 1 - 1.1920929e-07)), the clamp after denom.
+ * Rows with count[g] <= 0 keep their bits.  0 < min_opacity < 1. */
+int siu3r_mcmc_relocate(float* log_scales, float* logit_opacity, const int32_t* count, int64_t G, double min_opacity, void* stream);
+/* Row copy, one call per field [rows, r]: for j < n, field[d_j, :] = field[src[j], :] with d_j = dst[j], or G0 + j when dst is NULL (growth
+ * into rows G0 .. G0 + n - 1 of a buffer whose first G0 rows the caller filled).  With moments (m1 / m2 [rows, r], both or neither) rows d_j
+ * AND src[j] of both become zero: the source's moments belong to the Gaussian before its correction, the destination's to a Gaussian
+ * that no longer exists (gsplat zeroes the sources only).  Sources and destinations are disjoint by construction and this is not
+ * checked; an index outside 0 .. rows - 1 is skipped.  n >= 0, n * r < 2^31. */
+int siu3r_mcmc_copy_rows(float* field, float* m1, float* m2, int r, int64_t rows, const int32_t* src, const int32_t* dst, int64_t G0, int64_t n,
+                         void* stream);
+/* Noise, in place on means, fp32:  o = sigmoid(a[g]);  gate = 1 / (1 + exp(-100 (gate_opacity - o)));
+ *   means[g] += Sigma_g (noise[g] * gate * scaler),  Sigma_g = R(q / |q|) diag(exp(2 s)) R(q / |q|)^T,
+ * R as in siu3r_density_apply mode 1; noise [G,3]: the caller's unit normals; quats_xyzw 16-byte aligned. */
+int siu3r_mcmc_noise(float* means, const float* log_scales, const float* quats_xyzw, const float* logit_opacity, const float* noise, int64_t G,
+                     float gate_opacity, float scaler, void* stream);
+/* Regulariser lambda_o mean_g o + lambda_s mean_{g,k} exp(s[g,k]):  grad_opacity[g] += lambda_o o (1 - o) / G (the derivative by the logit),
+ * grad_scales[g,k] += lambda_s exp(s[g,k]) / (3 G); either gradient may be NULL (a frozen field).  value [2] (device) = the two terms, by
+ * fixed-order fp64 sums of the fp32 o and exp(s). */
+int siu3r_mcmc_regularize(const float* logit_opacity, const float* log_scales, int64_t G, float lambda_o, float lambda_s, float* grad_opacity,
+                          float* grad_scales, void* ws, float* value, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -172,6 +172,14 @@ SIGNATURES = {
     "siu3r_density_plan_ws": [_L],
     "siu3r_density_plan": [_P, _P, _P, _P, _P, _L, _F, _F, _F, _I, _F, _I, _P, _P, _P, _P, _P],
     "siu3r_density_apply": [_I, _P, _P, _P, _I, _L, _P, _P, _P, _P, _P, _P, _P, _P, _P],
+    "siu3r_mcmc_ws": [_L],
+    "siu3r_mcmc_weights": [_P, _L, _F, _I, _P, _P, _P],
+    "siu3r_mcmc_scan": [_P, _P, _L, _P, _P, _P, _P, _P],
+    "siu3r_mcmc_sample": [_P, _L, _P, _L, _P, _P, _P],
+    "siu3r_mcmc_relocate": [_P, _P, _P, _L, C.c_double, _P],
+    "siu3r_mcmc_copy_rows": [_P, _P, _P, _I, _L, _P, _P, _L, _L, _P],
+    "siu3r_mcmc_noise": [_P, _P, _P, _P, _P, _L, _F, _F, _P],
+    "siu3r_mcmc_regularize": [_P, _P, _L, _F, _F, _P, _P, _P, _P, _P],
     "siu3r_lift_ids": [_P, _I, _I, _I, _I, _I, _F, _I, C.c_uint32, _P, _P, _P, _P, _P],
     "siu3r_panoptic_stage1": [_P] * 20 + [_I] * 9 + [_F, _F, _F, C.c_uint32, _P],
     "siu3r_panoptic_qcl": [_P, _P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P],
@@ -181,6 +189,7 @@ _RESTYPES["siu3r_photo_loss_partials"] = C.c_int64
 _RESTYPES["siu3r_density_plan_ws"] = C.c_int64
 _RESTYPES["siu3r_depth_loss_ws"] = C.c_int64
 _RESTYPES["siu3r_gaussian_adam_ws"] = C.c_int64
+_RESTYPES["siu3r_mcmc_ws"] = C.c_int64
 
 _lib = None
 

@@ -6,7 +6,7 @@ refines second."""
 from __future__ import annotations
 
 import math
-from typing import Dict, List, Optional, Sequence, Tuple
+from typing import Dict, List, Optional, Sequence, Tuple, Union
 
 import torch
 
@@ -14,6 +14,7 @@ from . import raster
 from .cuda_splatting import render_cuda
 from .density import FIELDS, DensityControl, DensityStats, densify_and_prune, scene_extent
 from .losses import DEPTH_MODES, DEPTH_SPACES, depth_loss, photometric_loss
+from .mcmc import MCMCControl, grow, inject_noise, regularize, relocate
 from .optim import GaussianAdam, TorchAdam, log_linear, means_lr_schedule
 
 # Adam steps per field, those of the 3DGS training recipe (Kerbl et al. 2023): position 1.6e-4, scaling 5e-3, rotation 1e-3, opacity 5e-2,
@@ -104,7 +105,7 @@ def _check_optim_args(optimizer, sparse, means_lr_final, means_lr_extent_scale, 
 
 def refine_gaussians(means, scales, rotations, opacities, harmonics, images, c2w, Kn, near, far, bg, iters: int = 200, lambda_dssim: float = 0.2,
                      lrs: Optional[Dict[str, float]] = None, params: Sequence[str] = FIELDS, log_every: int = 1,
-                     density: Optional[DensityControl] = None, depths=None, depth_weights=None, lambda_depth=0.0, depth_mode: str = "l1",
+                     density: Union[DensityControl, MCMCControl, None] = None, depths=None, depth_weights=None, lambda_depth=0.0, depth_mode: str = "l1",
                      depth_space: str = "depth", depth_min_opacity: float = 0.5, optimizer: str = "torch", sparse: bool = False,
                      means_lr_final: Optional[float] = None, means_lr_extent_scale: bool = False,
                      sh_rest_lr_scale: float = 1.0) -> Tuple[Dict[str, torch.Tensor], List[float]]:
@@ -137,6 +138,18 @@ def refine_gaussians(means, scales, rotations, opacities, harmonics, images, c2w
     alone).  Every returned tensor then has the new row count, and the dict gains "density_events": one info dict per event
     (densify_and_prune's counts plus "iteration").  control.scene_extent = None costs one host read of the camera centres.
 
+    density may instead be a mcmc.MCMCControl: the budgeted strategy of Kheradmand et al. 2024 (3DGS as Markov-chain Monte Carlo).  No
+    statistics are kept (the render gets density_stats=None).  At the iterations control.events(iters) names, before that iteration's
+    render, mcmc.relocate moves every dead Gaussian (opacity <= min_opacity) onto a live one IN PLACE and mcmc.grow adds
+    int(grow_factor * G) - G rows, never past cap_max, over all five fields, free or frozen; the optimiser is rebound when the row count
+    changed (step count kept).  One host read per event (the number of dead rows).  After every backward mcmc.regularize adds the
+    gradients of opacity_reg * mean(opacity) and scale_reg * mean(scale) to the FREE opacity / scale leaves (a frozen field's term is a
+    constant and is left out), and `losses` logs the objective including both values.  After every optimiser step, when `means` is free and
+    noise_lr > 0, mcmc.inject_noise moves the means by covariance-shaped noise scaled by noise_lr * (this iteration's `means` rate,
+    schedule included), for every Gaussian (sparse=True skips no row here).  "density_events" then holds one dict per event: iteration,
+    rows_in, rows_out, relocated, added.  A cap_max below the starting row count, a non-finite or negative field and every <= 0 raise
+    ValueError before any device work.
+
     depths [V,H,W] with a non-zero lambda_depth adds a depth term: the objective of iteration t is photometric + lambda_t *
     losses.depth_loss(render depth, render opacity, depths, depth_weights, depth_mode, depth_space, depth_min_opacity) on the same
     render's depth (sum w z) and opacity (sum w) maps, both of which carry gradients.  depth_weights [V,H,W] (>= 0) is a per-pixel
@@ -164,6 +177,10 @@ def refine_gaussians(means, scales, rotations, opacities, harmonics, images, c2w
         if k not in FIELDS:
             raise ValueError(f"lrs: unknown field {k!r} (one of {FIELDS})")
         lr[k] = float(v)
+    mcmc = density if isinstance(density, MCMCControl) else None
+    classic = density if mcmc is None else None  # (the clone / split / prune control: every statement it had before MCMC keeps reading it)
+    if mcmc is not None:
+        mcmc.validate(means.shape[0])
     if int(iters) <= 0:
         params = ()
     dev = means.device
@@ -193,15 +210,21 @@ def refine_gaussians(means, scales, rotations, opacities, harmonics, images, c2w
     depth_losses: List[float] = []
     events: List[dict] = []
     extent = None  # of the scene: one host read unless the control names it
-    if (density is not None and free) or (means_lr_extent_scale and "means" in free):
-        extent = float(density.scene_extent) if density is not None and density.scene_extent is not None else scene_extent(c2w)
-    stats, densify_at, reset_at = None, (), ()
-    if density is not None and free:
-        density.thresholds(extent)  # (a bad extent raises here, not at the first event)
-        densify_at, reset_at = density.events(int(iters))
+    if (classic is not None and free) or (means_lr_extent_scale and "means" in free):
+        extent = float(classic.scene_extent) if classic is not None and classic.scene_extent is not None else scene_extent(c2w)
+    stats, densify_at, reset_at, mcmc_at = None, (), (), ()
+    if classic is not None and free:
+        classic.thresholds(extent)  # (a bad extent raises here, not at the first event)
+        densify_at, reset_at = classic.events(int(iters))
         stats = DensityStats(means.shape[0], dev)
-        noise_gen = torch.Generator(device=dev).manual_seed(int(density.seed))
+        noise_gen = torch.Generator(device=dev).manual_seed(int(classic.seed))
         unconstrained = {}  # the frozen fields in the form the density kernels read, made at the first event
+    if mcmc is not None and free:
+        mcmc_at = mcmc.events(int(iters))
+        noise_gen = torch.Generator(device=dev).manual_seed(int(mcmc.seed))  # the events' random words and the noise of every iteration
+        unconstrained = {k: _TO_PARAM[k](start[k]) for k in FIELDS if k not in free}  # (the regulariser and the noise read them from iteration 0 on)
+        reg_o = float(mcmc.opacity_reg) if "opacities" in free else 0.0  # a frozen field's term is a constant: neither added nor logged
+        reg_s = float(mcmc.scale_reg) if "scales" in free else 0.0
     means_lrs = None  # the `means` rate per iteration, where it is not the constant lr["means"] (optimizer="hip" only: _check_optim_args)
     if "means" in free and (means_lr_final is not None or means_lr_extent_scale):
         lr_scale = extent if means_lr_extent_scale else 1.0
@@ -235,9 +258,34 @@ def refine_gaussians(means, scales, rotations, opacities, harmonics, images, c2w
         stats = DensityStats(info["rows_out"], dev)
         return leaves
 
+    unc = lambda k, leaves: leaves[k].detach() if k in leaves else unconstrained[k]  # a field as the MCMC kernels read it
+
+    def mcmc_event(it: int) -> Dict[str, torch.Tensor]:
+        """relocate, then grow, before iteration `it`'s render, over all five fields and the free ones' moments.  Relocation works in place;
+        growth hands back longer tensors, and the optimiser moves to them (its step count stays); returns the leaves"""
+        nonlocal cov6_fixed
+        fields = {k: unc(k, free) for k in FIELDS}
+        moments = opt.moments
+        moved = relocate(fields, moments, mcmc, generator=noise_gen)
+        new_p, new_m, info = grow(fields, moments, mcmc, generator=noise_gen)
+        events.append(dict(iteration=it, rows_in=info["rows_in"], rows_out=info["rows_out"], relocated=moved["relocated"], added=info["added"]))
+        leaves = free
+        if info["added"] > 0:
+            leaves = {k: new_p[k].requires_grad_(True) for k in free}
+            opt.rebind(leaves, new_m)
+        for k in FIELDS:
+            if k not in leaves:
+                unconstrained[k] = new_p[k]
+                start[k] = _FROM_PARAM[k](new_p[k])
+        cov6_fixed = None if cov_moves else cov6_of(leaves)
+        return leaves
+
     for it in range(int(iters) if free else 0):
         if it in densify_at:
             free = density_event(it)
+        if it in mcmc_at:
+            with torch.no_grad():
+                free = mcmc_event(it)
         if it in reset_at and "opacities" in free:
             with torch.no_grad():
                 p = float(density.reset_opacity)
@@ -257,7 +305,15 @@ def refine_gaussians(means, scales, rotations, opacities, harmonics, images, c2w
             d_loss = depth_loss(dep, opa, depth_target, depth_conf, depth_mode, depth_space, depth_min_opacity)
             loss = photometric_loss(img, target, lambda_dssim) + lambdas_depth[it] * d_loss
         loss.backward()
+        if mcmc is not None and (reg_o > 0.0 or reg_s > 0.0):
+            reg = regularize(unc("opacities", free), unc("scales", free), reg_o, reg_s, free["opacities"].grad if reg_o > 0.0 else None,
+                             free["scales"].grad if reg_s > 0.0 else None)
+            loss = loss.detach() + reg.sum()
         opt.step(visible=radii, lrs=None if means_lrs is None else {"means": means_lrs[it]})
+        if mcmc is not None and "means" in free and float(mcmc.noise_lr) > 0.0:
+            scaler = float(mcmc.noise_lr) * (lr["means"] if means_lrs is None else means_lrs[it])
+            noise = torch.randn((free["means"].shape[0], 3), generator=noise_gen, device=dev, dtype=torch.float32)
+            inject_noise(free["means"].detach(), unc("scales", free), unc("rotations", free), unc("opacities", free), scaler, noise)
         if log_every and it % int(log_every) == 0:
             losses.append(float(loss.detach()))
             if lambdas_depth is not None:
