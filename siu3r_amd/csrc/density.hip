@@ -13,7 +13,7 @@
 //               75-float harmonics row is read and written by consecutive lanes.  keep: the bits; clone: the bits twice, the copy with zero
 //               moments; split: two children (means: + R(q / |q|) (exp(log_scale) o z), log-scales: - log 1.6), zero moments.
 // No kernel holds a float atomic, none allocates or synchronises with the host.
-#include "common.h"
+#include "gaussian_shared.h"
 
 namespace {
 
@@ -42,36 +42,6 @@ __global__ __launch_bounds__(NT) void accumulate_kernel(const float* __restrict_
   grad_accum[g] = acc;
   seen[g] = n;
   max_radius[g] = rmax;
-}
-
-// inclusive scan over the wave's 64 lanes
-__device__ inline int wave_scan(int v) {
-  const int lane = threadIdx.x & 63;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const int t = __shfl_up(v, o, 64);
-    if (lane >= o) v += t;
-  }
-  return v;
-}
-
-// inclusive scan over a workgroup of NW waves (wave totals through LDS); total = the workgroup's sum
-template <int NW>
-__device__ inline int block_scan(int v, int* wsum, int& total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  v = wave_scan(v);
-  __syncthreads();  // (the previous round's reads of wsum are over)
-  if (lane == 63) wsum[wave] = v;
-  __syncthreads();
-  int base = 0, t = 0;
-#pragma unroll
-  for (int w = 0; w < NW; ++w) {
-    const int s = wsum[w];
-    if (w < wave) base += s;
-    t += s;
-  }
-  total = t;
-  return v + base;
 }
 
 struct PlanArgs {
@@ -209,16 +179,11 @@ __global__ __launch_bounds__(NT) void apply_kernel(ApplyArgs a) {
   float child[2] = {v, v};
   if (MODE == LOG_SCALES) child[0] = child[1] = v - LOG_SPLIT;
   if (MODE == MEANS) {
-    // row e of R(q / |q|) in the operation order of quat_scale_cov6_kernel (raster.hip), the quaternion stored (x, y, z, w)
+    // row e of R(q / |q|), the quaternion stored (x, y, z, w)
     const float4 q = *(const float4*)(a.quats_xyzw + 4 * (int64_t)g);
-    float x = q.x, y = q.y, z = q.z, w = q.w;
-    const float inv = 1.0f / sqrtf(w * w + x * x + y * y + z * z);
-    w *= inv; x *= inv; y *= inv; z *= inv;
-    const float x2 = x * x, y2 = y * y, z2 = z * z, xy = x * y, xz = x * z, yz = y * z, wx = w * x, wy = w * y, wz = w * z;
-    float R0, R1, R2;
-    if (e == 0) R0 = 1.0f - 2.0f * (y2 + z2), R1 = 2.0f * (xy - wz), R2 = 2.0f * (xz + wy);
-    else if (e == 1) R0 = 2.0f * (xy + wz), R1 = 1.0f - 2.0f * (x2 + z2), R2 = 2.0f * (yz - wx);
-    else R0 = 2.0f * (xz - wy), R1 = 2.0f * (yz + wx), R2 = 1.0f - 2.0f * (x2 + y2);
+    float R[9];
+    quat_rotation(q.w, q.x, q.y, q.z, R);
+    const float R0 = e == 0 ? R[0] : e == 1 ? R[3] : R[6], R1 = e == 0 ? R[1] : e == 1 ? R[4] : R[7], R2 = e == 0 ? R[2] : e == 1 ? R[5] : R[8];
     const float* ls = a.log_scales + 3 * (int64_t)g;
     const float s0 = expf(ls[0]), s1 = expf(ls[1]), s2 = expf(ls[2]);
     const float* zn = a.noise + 6 * (int64_t)g;

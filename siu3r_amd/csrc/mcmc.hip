@@ -14,6 +14,7 @@
 //   regularize  the gradients of lambda_o mean(o) and lambda_s mean(exp(s)), and both values by a fixed-order reduction.
 // No kernel holds a float atomic, none allocates or synchronises with the host; two calls on equal inputs give equal bits.
 #include "block_reduce.h"
+#include "gaussian_shared.h"
 
 namespace {
 
@@ -36,37 +37,6 @@ __global__ __launch_bounds__(NT) void weights_kernel(const float* __restrict__ a
   const uint32_t v = o == o ? (uint32_t)rint(o * W_ONE) : 0u;  // (a NaN opacity is never drawn)
   w[g] = relocate && d ? 0u : v;
   dead[g] = d;
-}
-
-// inclusive scan over the wave's 64 lanes
-template <typename T>
-__device__ inline T wave_scan(T v) {
-  const int lane = threadIdx.x & 63;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const T t = __shfl_up(v, o, 64);
-    if (lane >= o) v += t;
-  }
-  return v;
-}
-
-// inclusive scan over a workgroup of NW waves (wave totals through LDS); total = the workgroup's sum
-template <int NW, typename T>
-__device__ inline T block_scan(T v, T* wsum, T& total) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  v = wave_scan(v);
-  __syncthreads();  // (the previous round's reads of wsum are over)
-  if (lane == 63) wsum[wave] = v;
-  __syncthreads();
-  T base = 0, t = 0;
-#pragma unroll
-  for (int w = 0; w < NW; ++w) {
-    const T s = wsum[w];
-    if (w < wave) base += s;
-    t += s;
-  }
-  total = t;
-  return v + base;
 }
 
 typedef unsigned long long u64;
@@ -206,15 +176,11 @@ __global__ __launch_bounds__(NT) void noise_kernel(float* __restrict__ means, co
   const float k = gate * scaler;
   const float* zn = noise + 3 * g;
   const float v0 = zn[0] * k, v1 = zn[1] * k, v2 = zn[2] * k;
-  // R(q / |q|) in the operation order of density.hip's split (mode 1), the quaternion stored (x, y, z, w)
+  // R(q / |q|), the quaternion stored (x, y, z, w)
   const float4 q = *(const float4*)(quats_xyzw + 4 * g);
-  float x = q.x, y = q.y, z = q.z, w = q.w;
-  const float inv = 1.0f / sqrtf(w * w + x * x + y * y + z * z);
-  w *= inv; x *= inv; y *= inv; z *= inv;
-  const float x2 = x * x, y2 = y * y, z2 = z * z, xy = x * y, xz = x * z, yz = y * z, wx = w * x, wy = w * y, wz = w * z;
-  const float R00 = 1.0f - 2.0f * (y2 + z2), R01 = 2.0f * (xy - wz), R02 = 2.0f * (xz + wy);
-  const float R10 = 2.0f * (xy + wz), R11 = 1.0f - 2.0f * (x2 + z2), R12 = 2.0f * (yz - wx);
-  const float R20 = 2.0f * (xz - wy), R21 = 2.0f * (yz + wx), R22 = 1.0f - 2.0f * (x2 + y2);
+  float R[9];
+  quat_rotation(q.w, q.x, q.y, q.z, R);
+  const float R00 = R[0], R01 = R[1], R02 = R[2], R10 = R[3], R11 = R[4], R12 = R[5], R20 = R[6], R21 = R[7], R22 = R[8];
   const float* ls = log_scales + 3 * g;
   // Sigma v = R (exp(2 s) o (R^T v))
   const float u0 = expf(2.0f * ls[0]) * (R00 * v0 + R10 * v1 + R20 * v2);

@@ -34,6 +34,7 @@
 #include <stdlib.h>
 
 #include "common.h"
+#include "gaussian_shared.h"
 #include "raster_shared.h"
 #include "raster_quad_lists.h"
 
@@ -989,12 +990,8 @@ __global__ void quat_scale_cov6_kernel(int64_t G, const float* quats, const floa
   const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (g >= G) return;
   const float4 q = *(const float4*)(quats + 4 * g);
-  float w = q.x, x = q.y, y = q.z, z = q.w;
-  const float inv = 1.0f / sqrtf(w * w + x * x + y * y + z * z);
-  w *= inv; x *= inv; y *= inv; z *= inv;
-  const float x2 = x * x, y2 = y * y, z2 = z * z, xy = x * y, xz = x * z, yz = y * z, wx = w * x, wy = w * y, wz = w * z;
-  const float R[9] = {1.0f - 2.0f * (y2 + z2), 2.0f * (xy - wz), 2.0f * (xz + wy), 2.0f * (xy + wz), 1.0f - 2.0f * (x2 + z2), 2.0f * (yz - wx),
-                      2.0f * (xz - wy), 2.0f * (yz + wx), 1.0f - 2.0f * (x2 + y2)};
+  float R[9];
+  quat_rotation(q.x, q.y, q.z, q.w, R);
   const float s0 = scales[3 * g], s1 = scales[3 * g + 1], s2 = scales[3 * g + 2];
   float M[9];
 #pragma unroll

@@ -22,6 +22,7 @@
 // radius_clip, tile rects and list membership, the sigma < 0 skip, the alpha_min cut-off, saturation and the alpha_max clamp are held
 // constant; the Jacobian clamp passes no gradient to the clamped component; a colour clamped at 0 passes none to its SH coefficients.
 #include "common.h"
+#include "gaussian_shared.h"
 #include "raster_shared.h"
 #include "raster_quad_lists.h"
 #include "raster_bwd_shared.h"
@@ -309,11 +310,9 @@ __global__ void quat_scale_cov6_bwd_kernel(int64_t G, const float* __restrict__ 
   const int64_t g = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (g >= G) return;
   const float4 q = *(const float4*)(quats + 4 * g);
-  const float inv = 1.0f / sqrtf(q.x * q.x + q.y * q.y + q.z * q.z + q.w * q.w);
+  float R[9];
+  const float inv = quat_rotation(q.x, q.y, q.z, q.w, R);
   const float w = q.x * inv, x = q.y * inv, y = q.z * inv, z = q.w * inv;
-  const float x2 = x * x, y2 = y * y, z2 = z * z, xy = x * y, xz = x * z, yz = y * z, wx = w * x, wy = w * y, wz = w * z;
-  const float R[9] = {1.0f - 2.0f * (y2 + z2), 2.0f * (xy - wz), 2.0f * (xz + wy), 2.0f * (xy + wz), 1.0f - 2.0f * (x2 + z2), 2.0f * (yz - wx),
-                      2.0f * (xz - wy), 2.0f * (yz + wx), 1.0f - 2.0f * (x2 + y2)};
   const float s[3] = {scales[3 * g], scales[3 * g + 1], scales[3 * g + 2]};
   float M[9];
 #pragma unroll

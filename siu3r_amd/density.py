@@ -59,6 +59,15 @@ class DensityStats:
                                                   _p(self.max_radius), _stream()))
 
 
+def event_iterations(start: int, every: int, stop: Optional[int], iters: int, who: str) -> List[int]:
+    """the schedule both controls share: start, start + every, ... up to and including stop (None: iters - every), never iteration 0 and
+    never an iteration a run of `iters` iterations does not reach.  `who` names the control in the error for every <= 0."""
+    if int(every) <= 0:
+        raise ValueError(f"{who}.every must be positive, got {every}")
+    stop = int(iters) - int(every) if stop is None else int(stop)
+    return [i for i in range(int(start), min(stop, int(iters) - 1) + 1, int(every)) if i > 0]
+
+
 @dataclass
 class DensityControl:
     """When and how refine.refine_gaussians changes the set.  grad_threshold (on the average NDC-space position gradient), percent_dense
@@ -89,14 +98,9 @@ class DensityControl:
         """(iterations that densify, iterations that reset the opacities) of a run of `iters` iterations: start, start + every, ... up to
         and including stop; resets at the multiples of reset_every up to stop.  Iteration 0 has no statistics and no moments yet and is
         never an event; neither is an iteration the run does not reach."""
-        iters = int(iters)
-        if int(self.every) <= 0:
-            raise ValueError(f"DensityControl.every must be positive, got {self.every}")
-        stop = iters - int(self.every) if self.stop is None else int(self.stop)
-        last = min(stop, iters - 1)
-        densify = [i for i in range(int(self.start), last + 1, int(self.every)) if i > 0]
-        resets = [i for i in range(int(self.reset_every), last + 1, int(self.reset_every))] if int(self.reset_every) > 0 else []
-        return densify, resets
+        densify = event_iterations(self.start, self.every, self.stop, iters, "DensityControl")
+        stop = int(iters) - int(self.every) if self.stop is None else int(self.stop)  # (the resets stop where the events do)
+        return densify, event_iterations(self.reset_every, self.reset_every, stop, iters, "DensityControl") if int(self.reset_every) > 0 else []
 
     def thresholds(self, extent: float) -> Dict[str, float]:
         """the float32 numbers the plan kernel compares against (computed once, on the host)"""
@@ -125,6 +129,16 @@ def _rows(t: torch.Tensor, G: int, name: str) -> torch.Tensor:
     return t
 
 
+def _check_params(params, moments, G: Optional[int] = None) -> int:  # (the five FIELDS and the moments given: float32 GPU tensors of G rows)
+    G = params["opacities"].shape[0] if G is None else G
+    _gpu(*params.values())
+    for k in FIELDS:
+        _rows(params[k], G, k)
+        if k in moments:
+            _rows(moments[k][0], G, k + " exp_avg"), _rows(moments[k][1], G, k + " exp_avg_sq")
+    return G
+
+
 def plan(stats: DensityStats, log_scales: torch.Tensor, logit_opacity: torch.Tensor, grad_threshold: float, log_dense_scale: float,
          logit_min_opacity: float, max_screen_radius: int = 0, log_max_world_scale: float = math.inf, grow: bool = True):
     """siu3r_density_plan -> (action [G] i32, offset [G] i32, totals [4] i32 = rows out / pruned / cloned / split), all on the device; no
@@ -149,12 +163,11 @@ def apply(params: Dict[str, torch.Tensor], moments: Dict[str, Tuple[torch.Tensor
     """siu3r_density_apply, one launch per field of `params` (all five FIELDS, unconstrained), each carrying the field's two Adam moments
     when `moments` has them -> (new params, new moments) of `rows_out` rows."""
     G = action.shape[0]
-    _gpu(action, offset, noise, *params.values())
+    _gpu(action, offset, noise)
     _rows(noise, G, "noise")
     if tuple(noise.shape) != (G, 2, 3):
         raise ValueError(f"noise must be [G, 2, 3] unit normals, got {tuple(noise.shape)}")
-    for k in FIELDS:
-        _rows(params[k], G, k)
+    _check_params(params, moments, G)
     lib = _lib.lib()
     new_p, new_m = {}, {}
     for k in FIELDS:
@@ -163,8 +176,7 @@ def apply(params: Dict[str, torch.Tensor], moments: Dict[str, Tuple[torch.Tensor
         dst = torch.empty((rows_out, *src.shape[1:]), dtype=torch.float32, device=src.device)
         m = moments.get(k)
         if m is not None:
-            _rows(m[0], G, k + " exp_avg"), _rows(m[1], G, k + " exp_avg_sq")
-            dm = (torch.empty_like(dst), torch.empty_like(dst))
+            dm =(torch.empty_like(dst), torch.empty_like(dst))
             new_m[k] = dm
         new_p[k] = dst
         if rows_out == 0:

@@ -19,7 +19,7 @@ import torch
 
 from . import _lib
 from ._lib import check
-from .density import FIELDS, _f32, _rows
+from .density import FIELDS, _check_params, _f32, _rows, event_iterations
 from .ops import _gpu, _p, _stream
 
 GATE_OPACITY = 0.005  # the noise gate's centre: gsplat's op_sigmoid(1 - o, k = 100, x0 = 0.995)
@@ -57,21 +57,15 @@ class MCMCControl:
             raise ValueError(f"MCMCControl.grow_factor must be >= 1, got {self.grow_factor!r}")
         if not 0.0 < float(self.min_opacity) < 1.0:
             raise ValueError(f"MCMCControl.min_opacity must lie inside (0, 1), got {self.min_opacity!r}")
-        if int(self.every) <= 0:
-            raise ValueError(f"MCMCControl.every must be positive, got {self.every}")
+        self.events(0)  # (every <= 0 raises there)
         if int(self.start) < 0 or (self.stop is not None and int(self.stop) < 0):
             raise ValueError(f"MCMCControl.start / stop must be >= 0, got {self.start!r} / {self.stop!r}")
         if G is not None and self.cap_max < int(G):
             raise ValueError(f"MCMCControl.cap_max = {self.cap_max} is below the {int(G)} Gaussians the run starts from (nothing is ever deleted)")
 
     def events(self, iters: int) -> List[int]:
-        """the iterations of a run of `iters` iterations that relocate and grow: start, start + every, ... up to and including stop.
-        Iteration 0 has no moments yet and is never an event; neither is an iteration the run does not reach."""
-        iters = int(iters)
-        if int(self.every) <= 0:
-            raise ValueError(f"MCMCControl.every must be positive, got {self.every}")
-        stop = iters - int(self.every) if self.stop is None else int(self.stop)
-        return [i for i in range(int(self.start), min(stop, iters - 1) + 1, int(self.every)) if i > 0]
+        """the iterations of a run of `iters` iterations that relocate and grow: the schedule of density.event_iterations"""
+        return event_iterations(self.start, self.every, self.stop, iters, "MCMCControl")
 
     def n_new(self, G: int) -> int:
         """how many rows an event adds to G: up to int(grow_factor * G), never past cap_max"""
@@ -208,17 +202,7 @@ def regularize(logit_opacity: torch.Tensor, log_scales: torch.Tensor, opacity_re
     return value
 
 
-# ---- the two halves of an event ------------------------------------------------------------------------------------------------------------
-def _check_params(params, moments) -> int:
-    G = params["opacities"].shape[0]
-    _gpu(*params.values())
-    for k in FIELDS:
-        _rows(params[k], G, k)
-        if k in moments:
-            _rows(moments[k][0], G, k + " exp_avg"), _rows(moments[k][1], G, k + " exp_avg_sq")
-    return G
-
-
+# ---- the two halves of an event, and the event -----------------------------------------------------------------------------------------------
 def _words(n: int, control: MCMCControl, rbits, generator, device) -> torch.Tensor:
     """n random words in [0, 2^32) as int64: the first n of the caller's, or drawn from `generator` (None: one seeded by control.seed)"""
     if rbits is not None:
@@ -282,3 +266,13 @@ def grow(params: Dict[str, torch.Tensor], moments: Dict[str, Tuple[torch.Tensor,
             new_m[k] = (grown(moments[k][0]), grown(moments[k][1]))
         copy_rows(new_p[k], new_m.get(k), sampled, None, G0=G)
     return new_p, new_m, info
+
+
+def event(params: Dict[str, torch.Tensor], moments: Dict[str, Tuple[torch.Tensor, torch.Tensor]], control: MCMCControl,
+          rbits: Optional[torch.Tensor] = None, generator: Optional[torch.Generator] = None):
+    """One MCMC event, in density.densify_and_prune's return shape: relocate (in place on `params`), then grow.  The random words are those
+    of relocate followed by those of grow: of `rbits` the first n_dead and the next n_new, else drawn in that order from `generator` (None:
+    each half seeds its own).  -> (new params, new moments, {"rows_in", "rows_out", "relocated", "added"}); nothing to add: the inputs."""
+    moved = relocate(params, moments, control, rbits, generator)
+    new_p, new_m, info = grow(params, moments, control, None if rbits is None else rbits[moved["relocated"]:], generator)
+    return new_p, new_m, dict(info, relocated=moved["relocated"])

@@ -6,6 +6,7 @@ refines second."""
 from __future__ import annotations
 
 import math
+from dataclasses import dataclass
 from typing import Dict, List, Optional, Sequence, Tuple, Union
 
 import torch
@@ -14,7 +15,7 @@ from . import raster
 from .cuda_splatting import render_cuda
 from .density import FIELDS, DensityControl, DensityStats, densify_and_prune, scene_extent
 from .losses import DEPTH_MODES, DEPTH_SPACES, depth_loss, photometric_loss
-from .mcmc import MCMCControl, grow, inject_noise, regularize, relocate
+from .mcmc import MCMCControl, event as mcmc_event, inject_noise, regularize
 from .optim import GaussianAdam, TorchAdam, log_linear, means_lr_schedule
 
 # Adam steps per field, those of the 3DGS training recipe (Kerbl et al. 2023): position 1.6e-4, scaling 5e-3, rotation 1e-3, opacity 5e-2,
@@ -103,6 +104,17 @@ def _check_optim_args(optimizer, sparse, means_lr_final, means_lr_extent_scale, 
     return optimizer == "hip"
 
 
+@dataclass
+class _Strategy:
+    """what refine_gaussians' loop needs to know of its control, made once before the loop (the defaults: no control)"""
+    events: Sequence[int] = ()            # iterations that begin with a density event
+    resets: Sequence[int] = ()            # iterations that begin with an opacity reset (clone / split / prune only)
+    stats: Optional[DensityStats] = None  # what every backward accumulates into (clone / split / prune only; renewed at each event)
+    reg_o: float = 0.0                    # MCMC: the regulariser weight of the free opacities; > 0 (or reg_s): that step follows the backward
+    reg_s: float = 0.0                    # ... of the free scales
+    noise_lr: float = 0.0                 # MCMC: > 0: the noise step follows the optimiser's
+
+
 def refine_gaussians(means, scales, rotations, opacities, harmonics, images, c2w, Kn, near, far, bg, iters: int = 200, lambda_dssim: float = 0.2,
                      lrs: Optional[Dict[str, float]] = None, params: Sequence[str] = FIELDS, log_every: int = 1,
                      density: Union[DensityControl, MCMCControl, None] = None, depths=None, depth_weights=None, lambda_depth=0.0, depth_mode: str = "l1",
@@ -177,10 +189,9 @@ def refine_gaussians(means, scales, rotations, opacities, harmonics, images, c2w
         if k not in FIELDS:
             raise ValueError(f"lrs: unknown field {k!r} (one of {FIELDS})")
         lr[k] = float(v)
-    mcmc = density if isinstance(density, MCMCControl) else None
-    classic = density if mcmc is None else None  # (the clone / split / prune control: every statement it had before MCMC keeps reading it)
-    if mcmc is not None:
-        mcmc.validate(means.shape[0])
+    budgeted = isinstance(density, MCMCControl)  # which of the two strategies a control is: said here, read where they differ
+    if budgeted:
+        density.validate(means.shape[0])
     if int(iters) <= 0:
         params = ()
     dev = means.device
@@ -195,12 +206,12 @@ def refine_gaussians(means, scales, rotations, opacities, harmonics, images, c2w
     near_t, far_t = as_v(near), as_v(far)
     bg_t = torch.tensor([[float(b) for b in bg]]).expand(V, 3)
 
-    # the free fields in their unconstrained form; `value` and `cov6_of` read a field through whichever leaves they are handed
+    # the free fields in their unconstrained form (an event may replace the leaves); `value` reads any field in the form the render takes
     free = {k: _TO_PARAM[k](start[k]).requires_grad_(True) for k in FIELDS if k in params}
-    value = lambda k, leaves: _FROM_PARAM[k](leaves[k]) if k in leaves else start[k]
+    value = lambda k: _FROM_PARAM[k](free[k]) if k in free else start[k]
     cov_moves = "scales" in free or "rotations" in free
-    cov6_of = lambda leaves: raster.quat_scale_to_cov6(torch.roll(value("rotations", leaves), 1, dims=-1), value("scales", leaves))
-    cov6_fixed = None if cov_moves else cov6_of(free)
+    cov6_of = lambda: raster.quat_scale_to_cov6(torch.roll(value("rotations"), 1, dims=-1), value("scales"))
+    cov6_fixed = None if cov_moves else cov6_of()
 
     if lambdas_depth is not None:
         depth_target = depths.detach().float().to(dev).contiguous()
@@ -209,22 +220,30 @@ def refine_gaussians(means, scales, rotations, opacities, harmonics, images, c2w
     losses: List[float] = []
     depth_losses: List[float] = []
     events: List[dict] = []
+    classic = density is not None and not budgeted
     extent = None  # of the scene: one host read unless the control names it
-    if (classic is not None and free) or (means_lr_extent_scale and "means" in free):
-        extent = float(classic.scene_extent) if classic is not None and classic.scene_extent is not None else scene_extent(c2w)
-    stats, densify_at, reset_at, mcmc_at = None, (), (), ()
-    if classic is not None and free:
-        classic.thresholds(extent)  # (a bad extent raises here, not at the first event)
-        densify_at, reset_at = classic.events(int(iters))
-        stats = DensityStats(means.shape[0], dev)
-        noise_gen = torch.Generator(device=dev).manual_seed(int(classic.seed))
-        unconstrained = {}  # the frozen fields in the form the density kernels read, made at the first event
-    if mcmc is not None and free:
-        mcmc_at = mcmc.events(int(iters))
-        noise_gen = torch.Generator(device=dev).manual_seed(int(mcmc.seed))  # the events' random words and the noise of every iteration
-        unconstrained = {k: _TO_PARAM[k](start[k]) for k in FIELDS if k not in free}  # (the regulariser and the noise read them from iteration 0 on)
-        reg_o = float(mcmc.opacity_reg) if "opacities" in free else 0.0  # a frozen field's term is a constant: neither added nor logged
-        reg_s = float(mcmc.scale_reg) if "scales" in free else 0.0
+    if (classic and free) or (means_lr_extent_scale and "means" in free):
+        extent = float(density.scene_extent) if classic and density.scene_extent is not None else scene_extent(c2w)
+    strategy = _Strategy()  # (no control, or nothing free: no events, no statistics, no extra steps)
+    if density is not None and free:
+        noise_gen = torch.Generator(device=dev).manual_seed(int(density.seed))  # the events' split noise, or their random words and every iteration's noise
+        if classic:
+            density.thresholds(extent)  # (a bad extent raises here, not at the first event)
+            strategy = _Strategy(*density.events(int(iters)), stats=DensityStats(means.shape[0], dev))
+        else:  # (a frozen field's regulariser term is a constant: neither added nor logged; frozen means take no noise)
+            strategy = _Strategy(density.events(int(iters)), reg_o=float(density.opacity_reg) if "opacities" in free else 0.0,
+                                 reg_s=float(density.scale_reg) if "scales" in free else 0.0, noise_lr=float(density.noise_lr) if "means" in free else 0.0)
+    frozen = {}  # the frozen fields in the form the density / MCMC kernels read, each made when `unc` first asks for it
+
+    def unc(k: str) -> torch.Tensor:
+        """field k in unconstrained form: the free leaf, or a frozen field through log / logit, made when first asked for and kept (an event
+        replaces it by its output).  Only an event and the MCMC regulariser / noise ask, so without a control nothing is ever computed here;
+        `start`, which the render reads and the caller gets back, keeps the input's bits until the first event that runs (then, not before,
+        frozen scales / opacities make their round trip)."""
+        if k not in free and k not in frozen:
+            frozen[k] = _TO_PARAM[k](start[k])
+        return free[k].detach() if k in free else frozen[k]
+
     means_lrs = None  # the `means` rate per iteration, where it is not the constant lr["means"] (optimizer="hip" only: _check_optim_args)
     if "means" in free and (means_lr_final is not None or means_lr_extent_scale):
         lr_scale = extent if means_lr_extent_scale else 1.0
@@ -234,68 +253,42 @@ def refine_gaussians(means, scales, rotations, opacities, harmonics, images, c2w
         free_lrs = {k: lr[k] for k in free}
         opt = GaussianAdam(free, free_lrs, eps=1e-15, sh_rest_lr_scale=float(sh_rest_lr_scale)) if hip else TorchAdam(free, free_lrs, eps=1e-15)
 
-    def density_event(it: int) -> Dict[str, torch.Tensor]:
-        """clone / split / prune before iteration `it`'s render: every field and the free ones' moments go through densify_and_prune, the
-        optimiser moves to the new leaves (its step count stays), the frozen fields and the statistics follow; returns the new leaves"""
-        nonlocal stats, cov6_fixed
-        for k in FIELDS:
-            if k not in free and k not in unconstrained:
-                unconstrained[k] = _TO_PARAM[k](start[k])
-        moments = opt.moments
-        noise = torch.randn((stats.G, 2, 3), generator=noise_gen, device=dev, dtype=torch.float32)
-        new_p, new_m, info = densify_and_prune({k: (free[k].detach() if k in free else unconstrained[k]) for k in FIELDS}, moments, stats, density,
-                                               extent, noise)
-        if info["rows_out"] == 0:
-            raise RuntimeError(f"density control pruned every Gaussian at iteration {it}: {info}")
+    def event(it: int):
+        """one density event before iteration `it`'s render: all five fields in unconstrained form and the free ones' moments go through the
+        strategy's one function (clone / split / prune, or relocate in place and grow); where it hands back new tensors they become the
+        leaves and the optimiser moves to them (its step count stays); the frozen fields, cov6_fixed and the classic statistics follow"""
+        nonlocal free, cov6_fixed
+        fields = {k: unc(k) for k in FIELDS}
+        if classic:
+            noise = torch.randn((strategy.stats.G, 2, 3), generator=noise_gen, device=dev, dtype=torch.float32)
+            new_p, new_m, info = densify_and_prune(fields, opt.moments, strategy.stats, density, extent, noise)
+            if info["rows_out"] == 0:
+                raise RuntimeError(f"density control pruned every Gaussian at iteration {it}: {info}")
+            strategy.stats = DensityStats(info["rows_out"], dev)
+        else:
+            new_p, new_m, info = mcmc_event(fields, opt.moments, density, generator=noise_gen)
         events.append(dict(info, iteration=it))
-        leaves = {k: new_p[k].requires_grad_(True) for k in free}
-        for k in FIELDS:
-            if k not in leaves:
-                unconstrained[k] = new_p[k]
-                start[k] = _FROM_PARAM[k](new_p[k])
-        opt.rebind(leaves, new_m)
-        cov6_fixed = None if cov_moves else cov6_of(leaves)
-        stats = DensityStats(info["rows_out"], dev)
-        return leaves
-
-    unc = lambda k, leaves: leaves[k].detach() if k in leaves else unconstrained[k]  # a field as the MCMC kernels read it
-
-    def mcmc_event(it: int) -> Dict[str, torch.Tensor]:
-        """relocate, then grow, before iteration `it`'s render, over all five fields and the free ones' moments.  Relocation works in place;
-        growth hands back longer tensors, and the optimiser moves to them (its step count stays); returns the leaves"""
-        nonlocal cov6_fixed
-        fields = {k: unc(k, free) for k in FIELDS}
-        moments = opt.moments
-        moved = relocate(fields, moments, mcmc, generator=noise_gen)
-        new_p, new_m, info = grow(fields, moments, mcmc, generator=noise_gen)
-        events.append(dict(iteration=it, rows_in=info["rows_in"], rows_out=info["rows_out"], relocated=moved["relocated"], added=info["added"]))
-        leaves = free
-        if info["added"] > 0:
-            leaves = {k: new_p[k].requires_grad_(True) for k in free}
-            opt.rebind(leaves, new_m)
-        for k in FIELDS:
-            if k not in leaves:
-                unconstrained[k] = new_p[k]
-                start[k] = _FROM_PARAM[k](new_p[k])
-        cov6_fixed = None if cov_moves else cov6_of(leaves)
-        return leaves
+        if new_p is not fields:  # (MCMC with nothing to add keeps its leaves)
+            free = {k: new_p[k].requires_grad_(True) for k in free}
+            opt.rebind(free, new_m)
+        frozen.update({k: new_p[k] for k in FIELDS if k not in free})
+        start.update({k: _FROM_PARAM[k](v) for k, v in frozen.items()})
+        cov6_fixed = None if cov_moves else cov6_of()
 
     for it in range(int(iters) if free else 0):
-        if it in densify_at:
-            free = density_event(it)
-        if it in mcmc_at:
+        if it in strategy.events:
             with torch.no_grad():
-                free = mcmc_event(it)
-        if it in reset_at and "opacities" in free:
+                event(it)
+        if it in strategy.resets and "opacities" in free:
             with torch.no_grad():
                 p = float(density.reset_opacity)
                 free["opacities"].clamp_(max=math.log(p / (1.0 - p)))
                 opt.zero_moments("opacities")
         opt.zero_grad(set_to_none=True)
-        cov6 = cov6_of(free) if cov_moves else cov6_fixed
-        rendered = render_cuda(c2w, Kn, near_t, far_t, (H, W), bg_t, value("means", free)[None].expand(V, -1, -1), cov6[None].expand(V, -1, -1),
-                               value("harmonics", free)[None].expand(V, -1, -1, -1), value("opacities", free)[None].expand(V, -1),
-                               density_stats=stats, return_aux=want_aux)
+        cov6 = cov6_of() if cov_moves else cov6_fixed
+        rendered = render_cuda(c2w, Kn, near_t, far_t, (H, W), bg_t, value("means")[None].expand(V, -1, -1), cov6[None].expand(V, -1, -1),
+                               value("harmonics")[None].expand(V, -1, -1, -1), value("opacities")[None].expand(V, -1),
+                               density_stats=strategy.stats, return_aux=want_aux)
         img, dep = rendered[0], rendered[1]
         opa = _aux_cat(rendered[2], "opacity") if lambdas_depth is not None else None
         radii = _aux_cat(rendered[2], "radii") if sparse else None
@@ -305,21 +298,21 @@ def refine_gaussians(means, scales, rotations, opacities, harmonics, images, c2w
             d_loss = depth_loss(dep, opa, depth_target, depth_conf, depth_mode, depth_space, depth_min_opacity)
             loss = photometric_loss(img, target, lambda_dssim) + lambdas_depth[it] * d_loss
         loss.backward()
-        if mcmc is not None and (reg_o > 0.0 or reg_s > 0.0):
-            reg = regularize(unc("opacities", free), unc("scales", free), reg_o, reg_s, free["opacities"].grad if reg_o > 0.0 else None,
-                             free["scales"].grad if reg_s > 0.0 else None)
+        if strategy.reg_o > 0.0 or strategy.reg_s > 0.0:
+            reg = regularize(unc("opacities"), unc("scales"), strategy.reg_o, strategy.reg_s, free["opacities"].grad if strategy.reg_o > 0.0 else None,
+                             free["scales"].grad if strategy.reg_s > 0.0 else None)
             loss = loss.detach() + reg.sum()
         opt.step(visible=radii, lrs=None if means_lrs is None else {"means": means_lrs[it]})
-        if mcmc is not None and "means" in free and float(mcmc.noise_lr) > 0.0:
-            scaler = float(mcmc.noise_lr) * (lr["means"] if means_lrs is None else means_lrs[it])
+        if strategy.noise_lr > 0.0:
+            scaler = strategy.noise_lr * (lr["means"] if means_lrs is None else means_lrs[it])
             noise = torch.randn((free["means"].shape[0], 3), generator=noise_gen, device=dev, dtype=torch.float32)
-            inject_noise(free["means"].detach(), unc("scales", free), unc("rotations", free), unc("opacities", free), scaler, noise)
+            inject_noise(unc("means"), unc("scales"), unc("rotations"), unc("opacities"), scaler, noise)
         if log_every and it % int(log_every) == 0:
             losses.append(float(loss.detach()))
             if lambdas_depth is not None:
                 depth_losses.append(float(d_loss.detach()))
     with torch.no_grad():
-        out = {k: (value(k, free).detach().clone() if k in free else start[k].clone()) for k in FIELDS}
+        out = {k: value(k).detach().clone() for k in FIELDS}
         out["covariances"] = covariances_from(out["rotations"], out["scales"])
         if density is not None:
             out["density_events"] = events

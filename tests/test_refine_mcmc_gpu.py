@@ -38,7 +38,7 @@ def _run(density, **kw):
     from siu3r_amd.refine import refine_gaussians
 
     s = _scene()
-    out, losses = refine_gaussians(*(s["start"][k] for k in FIELDS), s["targets"], s["train"], s["Kt"], NEAR, FAR, BG, iters=ITERS, density=density, **kw)
+    out, losses = refine_gaussians(*(s["start"][k] for k in FIELDS), s["targets"], s["train"], s["Kt"], NEAR, FAR, BG, density=density, **{"iters": ITERS, **kw})
     for k in FIELDS:
         assert torch.equal(s["start"][k], s["keep"][k]), f"input {k} was modified"
     return out, losses
@@ -99,6 +99,22 @@ def test_at_the_cap_the_row_count_never_changes(optimizer):
     out, _ = _run(MCMCControl(cap_max=G + 77, start=10, every=10), params=("harmonics",), **kw)
     ev = _check_events(out, G + 77)
     assert [e["added"] for e in ev] == [77, 0]
+
+
+@pytest.mark.parametrize("optimizer", ["torch", "hip"])
+@pytest.mark.parametrize("control", ["classic", "mcmc"])
+def test_before_the_first_event_a_control_leaves_the_frozen_fields_bit_identical(control, optimizer):
+    """a run that ends before the control's `start`: no event runs, so no frozen field may have gone through its unconstrained form
+    (sigmoid(logit(x)) is not x, exp(log(x)) is not x): means, scales, rotations and opacities come back with the input's bits"""
+    from siu3r_amd.density import DensityControl
+    from siu3r_amd.mcmc import MCMCControl
+
+    density = DensityControl(start=100) if control == "classic" else MCMCControl(cap_max=10**6, start=100)
+    out, losses = _run(density, params=("harmonics",), iters=5, optimizer=optimizer)
+    assert out["density_events"] == [] and len(losses) == 5
+    for k in ("means", "scales", "rotations", "opacities"):
+        assert torch.equal(out[k], _scene()["start"][k]), f"frozen {k} changed without an event"
+    assert not torch.equal(out["harmonics"], _scene()["start"]["harmonics"])
 
 
 def test_all_fields_free_the_objective_goes_down():
