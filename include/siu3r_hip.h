@@ -26,7 +26,7 @@ extern "C" {
 #define SIU3R_F64 3
 
 const char* siu3r_last_error(void);
-#define SIU3R_ABI_VERSION 11 /* 11: siu3r_attention_plan (what siu3r_attention launches for a parameter block); 10: siu3r_stem7x7_x3 (the Gaussian heads' stem as one dedicated kernel), siu3r_proj_rows_x3 (the heads' last 1 x 1 convolutions as row streams); 9: siu3r_raster_project_c2w + siu3r_raster_cam.k2_near / k2_far (the reference renderer's own pose tensors, consumed on the device), siu3r_raster_tune (replaces the SIU3R_FEAT_FORM / SIU3R_FEAT_NP environment switches; the shared-batch matrix-core composite is gone: no workspace = 32-channel kernel); 8: LPIPS (siu3r_maxpool2x2s2, siu3r_lpips_layer); 7: device-side poses for the gsplat seam (siu3r_raster_project_dp, siu3r_sh_eval_dp, siu3r_blend_background_dp), precomputed K2 colours (sh_degree < 0), all-channel list composite; 6: pre-split bf16x3 activations (siu3r_gemm_params.c_x3 / a_x3, siu3r_gemm_plan_t.a_x3_ok / c_x3_ok), siu3r_attn_params.kv_bxor / kv_x3, siu3r_gemm_params.c_x3_col0; 5: siu3r_raster_sort takes stage 1's counters (culled Gaussians leave the sort), NaN-poisoned views on entry overflow, siu3r_gemm_tune key 4; 4: siu3r_gemm_plan, split-K workspace capacities + self-resetting tickets, tile_cfg; 3: view-batched sort-free rasterizer */
+#define SIU3R_ABI_VERSION 12 /* 12: siu3r_gemm_plan_t.skinny_path (which code multiplies the remainder rows); 11: siu3r_attention_plan (what siu3r_attention launches for a parameter block); 10: siu3r_stem7x7_x3 (the Gaussian heads' stem as one dedicated kernel), siu3r_proj_rows_x3 (the heads' last 1 x 1 convolutions as row streams); 9: siu3r_raster_project_c2w + siu3r_raster_cam.k2_near / k2_far (the reference renderer's own pose tensors, consumed on the device), siu3r_raster_tune (replaces the SIU3R_FEAT_FORM / SIU3R_FEAT_NP environment switches; the shared-batch matrix-core composite is gone: no workspace = 32-channel kernel); 8: LPIPS (siu3r_maxpool2x2s2, siu3r_lpips_layer); 7: device-side poses for the gsplat seam (siu3r_raster_project_dp, siu3r_sh_eval_dp, siu3r_blend_background_dp), precomputed K2 colours (sh_degree < 0), all-channel list composite; 6: pre-split bf16x3 activations (siu3r_gemm_params.c_x3 / a_x3, siu3r_gemm_plan_t.a_x3_ok / c_x3_ok), siu3r_attn_params.kv_bxor / kv_x3, siu3r_gemm_params.c_x3_col0; 5: siu3r_raster_sort takes stage 1's counters (culled Gaussians leave the sort), NaN-poisoned views on entry overflow, siu3r_gemm_tune key 4; 4: siu3r_gemm_plan, split-K workspace capacities + self-resetting tickets, tile_cfg; 3: view-batched sort-free rasterizer */
 int siu3r_abi_version(void);
 
 /* ---- seam 1: curope.rope_2d(tokens, positions, base, fwd)
@@ -41,7 +41,9 @@ int siu3r_rope2d(void* tokens, int dtype, int B, int N, int H, int D, int64_t st
  * (reference: croco/blocks.py:58-79,94-112; heads/dpt_block.py; vit_adapter.py; video_seg_decoder.py).
  * C[M,N] = epilogue(A[M,K] * W[N,K]^T).  W is pre-packed bf16 [N, Kpad] (Kpad % 64 == 0, zero padded);
  * w_lo (may be NULL) holds the bf16 residual of the fp32 weight and enables the 3-pass
- * "bf16x3" mode (A must then be fp32): C = Ahi*Whi + Ahi*Wlo + Alo*Whi, ~fp32 accuracy. */
+ * "bf16x3" mode (A must then be fp32): C = Ahi*Whi + Ahi*Wlo + Alo*Whi, ~fp32 accuracy.
+ * Dense A: the elements A[m, k .. kpad) behind a row (inside the operand: the row stride's slack or the next row) MAY be fetched and
+ * multiplied by the zero padding of W, so they must be finite; nothing is read beyond element (m-1)*lda + k of a batch item. */
 typedef struct {
   const void* a;          /* activations */
   const void* w_hi;       /* bf16 [N,Kpad] */
@@ -136,12 +138,16 @@ typedef struct {
 int siu3r_gemm(const siu3r_gemm_params* p, void* stream);
 /* What siu3r_gemm will launch for these parameters (same decision function): tile family, tile, split-K slices, whether the last
  * rows go to the skinny kernel, the split-K workspace it needs (fp32 elements / int32 counters) and the kernel's name as rocprofv3
- * prints it.  Callers that attach a workspace of at least this size get the split; smaller workspaces reduce splitk. */
+ * prints it.  Callers that attach a workspace of at least this size get the split; smaller workspaces reduce splitk.
+ * skinny_path says which code multiplies the skinny_rows remainder rows: 0 = there are none, 1 = extra workgroups of the tile launch
+ * itself (kernel), 2 = the MFMA skinny kernel (siu3r_gemm_pp::gemm_skinny_kernel), 3 = the matrix-vector kernel
+ * (siu3r_gemm_pp::gemm_skinny_gemv_kernel); 2 and 3 are a second launch, or the only one when skinny_rows == m. */
 typedef struct {
   int32_t tile_cfg, bm, bn, splitk, skinny_rows, counters;
   int64_t ws_floats;
   char kernel[160];
   int32_t a_x3_ok, c_x3_ok; /* this plan can read A as pre-split planes (a_x3) / write the output as planes (c_x3) */
+  int32_t skinny_path;      /* 0 none, 1 carried by the tile launch, 2 MFMA skinny kernel, 3 matrix-vector kernel */
 } siu3r_gemm_plan_t;
 int siu3r_gemm_plan(const siu3r_gemm_params* p, siu3r_gemm_plan_t* out);
 /* tuning aid (tools/, tests): key 0 = process-wide default of siu3r_gemm_params.tile_cfg (SIU3R_TILE_*; also env SIU3R_GEMM_PP), key 1 =

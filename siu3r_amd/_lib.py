@@ -47,7 +47,7 @@ class GemmPlan(C.Structure):
     """siu3r_gemm_plan_t: what siu3r_gemm launches for a parameter block."""
     _fields_ = [
         ("tile_cfg", C.c_int32), ("bm", C.c_int32), ("bn", C.c_int32), ("splitk", C.c_int32), ("skinny_rows", C.c_int32),
-        ("counters", C.c_int32), ("ws_floats", C.c_int64), ("kernel", C.c_char * 160), ("a_x3_ok", C.c_int32), ("c_x3_ok", C.c_int32),
+        ("counters", C.c_int32), ("ws_floats", C.c_int64), ("kernel", C.c_char * 160), ("a_x3_ok", C.c_int32), ("c_x3_ok", C.c_int32), ("skinny_path", C.c_int32),
     ]
 
 
@@ -100,7 +100,7 @@ class AdamField(C.Structure):
 
 # name -> argtypes; restype is c_int unless listed in _RESTYPES.  Mirrors include/siu3r_hip.h.
 _P, _I, _L, _F = C.c_void_p, C.c_int, C.c_int64, C.c_float
-ABI_VERSION = 11  # SIU3R_ABI_VERSION of include/siu3r_hip.h these ctypes declarations mirror
+ABI_VERSION = 12  # SIU3R_ABI_VERSION of include/siu3r_hip.h these ctypes declarations mirror
 
 SIGNATURES = {
     "siu3r_last_error": [],

@@ -25,7 +25,8 @@ int siu3r_gemm_pp_mode(const siu3r_gemm_params& p);                           //
 void siu3r_gemm_pp_name(const siu3r_gemm_params& p, int cfg, char* buf, int n);
 int siu3r_gemm_pp_launch(const siu3r_gemm_params& p, int cfg, void* stream);
 int siu3r_gemm_skinny_launch(const siu3r_gemm_params& p, void* stream);
-bool siu3r_gemm_pp_folds_skinny(const siu3r_gemm_params& p);
+int siu3r_gemm_skinny_path(const siu3r_gemm_params& p);           // gemm_pp.hip: who multiplies rows [m_main, m) (siu3r_gemm_plan_t.skinny_path)
+int siu3r_gemm_dma_kspl();                                        // gemm_dma.hip: K-split template argument of the 128 x 64 LDS-DMA kernels it launches
 bool siu3r_gemm_pp_a_x3_ok(const siu3r_gemm_params& p);          // pre-split A planes readable / output planes writable by a ping-pong launch
 bool siu3r_gemm_pp_c_x3_ok(const siu3r_gemm_params& p, int cfg);
 static const bool g_disable_dma = getenv("SIU3R_GEMM_NO_DMA") != nullptr;     // debugging / A-B switch
@@ -457,6 +458,11 @@ void plan(const siu3r_gemm_params& p, siu3r_gemm_plan_t& pl) {
   pl.bn = c.bn;
   pl.splitk = best_s;
   pl.skinny_rows = best_skinny;
+  if (c.cfg > 0 && best_skinny > 0) {
+    siu3r_gemm_params q = p;
+    q.m_main = p.m - best_skinny;
+    pl.skinny_path = siu3r_gemm_skinny_path(q);
+  }
   if (c.cfg < 0) {
     // the 128 x 64 family: 128 x 128 tiles only for A/B runs (SIU3R_GEMM_NARROW_MAX); register-staged kernels never split
     const int64_t tiles128 = (int64_t)((p.m + BM - 1) / BM) * ((p.n + 127) / 128) * Z;
@@ -474,9 +480,9 @@ void plan(const siu3r_gemm_params& p, siu3r_gemm_plan_t& pl) {
   if (c.cfg > 0) {
     siu3r_gemm_pp_name(p, c.cfg, pl.kernel, sizeof(pl.kernel));
   } else if (x3 && dma_mode >= 0 && pl.bn == 64) {
-    snprintf(pl.kernel, sizeof(pl.kernel), "siu3r_gemm_dma::gemm_dma_x3_kernel<%d, %s, 2, %s>", dma_mode, tf(dma_mode == 1 && p.relu_in), tf(dma_mode == 0 && p.ln_stats));
+    snprintf(pl.kernel, sizeof(pl.kernel), "siu3r_gemm_dma::gemm_dma_x3_kernel<%d, %s, %d, %s>", dma_mode, tf(dma_mode == 1 && p.relu_in), siu3r_gemm_dma_kspl(), tf(dma_mode == 0 && p.ln_stats));
   } else if (!x3 && !p.w_lo && dma_mode >= 0) {
-    snprintf(pl.kernel, sizeof(pl.kernel), "siu3r_gemm_dma::gemm_dma_kernel<%d, %d, %s, 2, %s>", pl.bn / 64, dma_mode, tf(dma_mode == 1 && p.relu_in), tf(dma_mode == 0 && p.ln_stats));
+    snprintf(pl.kernel, sizeof(pl.kernel), "siu3r_gemm_dma::gemm_dma_kernel<%d, %d, %s, %d, %s>", pl.bn / 64, dma_mode, tf(dma_mode == 1 && p.relu_in), siu3r_gemm_dma_kspl(), tf(dma_mode == 0 && p.ln_stats));
   } else {
     snprintf(pl.kernel, sizeof(pl.kernel), "gemm_kernel<%d, %d, %d%s>", p.a_dtype == SIU3R_F32 ? 1 : 0, p.w_lo ? 1 : 0, pl.bn / 64, p.ln_stats ? ", true" : "");
   }
@@ -557,7 +563,7 @@ extern "C" int siu3r_gemm(const siu3r_gemm_params* pp, void* stream) {
       const int rc = siu3r_gemm_pp_launch(q, pl.tile_cfg, stream);
       if (rc) return rc;
     }
-    if (pl.skinny_rows > 0 && !(q.m_main > 0 && siu3r_gemm_pp_folds_skinny(q))) {
+    if (pl.skinny_rows > 0 && siu3r_gemm_skinny_path(q) != 1) {
       q.splitk = 0;
       return siu3r_gemm_skinny_launch(q, stream);
     }

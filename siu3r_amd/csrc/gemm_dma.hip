@@ -785,6 +785,13 @@ int siu3r_gemm_dma_x3_mode(const siu3r_gemm_params& p) {
   return p.relu_in ? -1 : 2;
 }
 
+// K-split template argument (KSPL) of the 128 x 64 kernels launched below: 2 = 8-wave workgroups whose wave halves share every K tile;
+// 1 under the A/B switch SIU3R_GEMM_NO_KSPLIT (4-wave workgroups).  Also what siu3r_gemm_plan prints in the kernel's name.
+int siu3r_gemm_dma_kspl() {
+  static const bool no_ksplit = getenv("SIU3R_GEMM_NO_KSPLIT") != nullptr;
+  return no_ksplit ? 1 : 2;
+}
+
 // Called by siu3r_gemm() (gemm.hip) for bf16 activations without the bf16x3 split, dense or conv gather.
 // Returns 1 when the problem is outside what the buffer-addressed kernels cover (the caller then uses the
 // register-staged kernel): operands of 4 GiB or more, or a fused input ReLU outside MODE 1.
@@ -805,8 +812,7 @@ int siu3r_gemm_dma_launch(const siu3r_gemm_params& p, int ni, void* stream) {
   const int tiles = 8 * p.map_rm * p.map_rn;
   dim3 grid(tiles, p.splitk > 1 ? p.splitk : 1, p.batch > 0 ? p.batch : 1);
   hipStream_t s = (hipStream_t)stream;
-  static const bool no_ksplit = getenv("SIU3R_GEMM_NO_KSPLIT") != nullptr;  // A/B switch: 4-wave workgroups for the 128x64 tile
-  const int kspl = no_ksplit ? 1 : 2;
+  const int kspl = siu3r_gemm_dma_kspl();
   dim3 block(256 * kspl);
 #define SIU3R_DMA_LAUNCH(NI_, MODE_, RELU_, KS_) hipLaunchKernelGGL((gemm_dma_kernel<NI_, MODE_, RELU_, KS_>), grid, block, 0, s, p)
 #define SIU3R_DMA_MODES(NI_, KS_)                                      \
@@ -849,7 +855,7 @@ int siu3r_gemm_dma_x3_launch(const siu3r_gemm_params& p, void* stream) {
   const int tiles = 8 * p.map_rm * p.map_rn;
   dim3 grid(tiles, p.splitk > 1 ? p.splitk : 1, p.batch > 0 ? p.batch : 1);
   hipStream_t s = (hipStream_t)stream;
-  static const bool no_ksplit = getenv("SIU3R_GEMM_NO_KSPLIT") != nullptr;
+  const bool no_ksplit = siu3r_gemm_dma_kspl() == 1;
   if (mode == 0 && p.ln_stats) {
     if (no_ksplit) hipLaunchKernelGGL((gemm_dma_x3_kernel<0, false, 1, true>), grid, dim3(256), 0, s, p);
     else hipLaunchKernelGGL((gemm_dma_x3_kernel<0, false, 2, true>), grid, dim3(512), 0, s, p);

@@ -258,6 +258,25 @@ int siu3r_gemm_pp_launch(const siu3r_gemm_params& pin, int cfg, void* stream) {
   return 0;
 }
 
+// Which code multiplies the remainder rows [p.m_main, p.m) of a launch planned with skinny rows (siu3r_gemm_plan_t.skinny_path): 1 = extra
+// workgroups of the ping-pong launch, 2 = the MFMA skinny kernel, 3 = the matrix-vector kernel.  The one predicate of siu3r_gemm, of
+// siu3r_gemm_skinny_launch and of the plan query.
+int siu3r_gemm_skinny_path(const siu3r_gemm_params& p) {
+  if (siu3r_gemm_pp_folds_skinny(p)) return 1;
+#ifndef SIU3R_PP_MINI
+  // at most four rows: the matrix-vector kernel (16-byte aligned A rows, K % 4 == 0, the rows fit its LDS)
+  const bool x3 = p.w_x3 != nullptr && p.a_dtype == SIU3R_F32;
+  const int rows = p.m - p.m_main, esz = x3 ? 4 : 2;
+  static const bool no_gemv = getenv("SIU3R_GEMM_NO_GEMV") != nullptr;
+  // (measured, tools/mb_skinny.py: the MFMA kernel above wins at K = 1024 -- 12.7 vs 14.7 us, both mostly fixed cost -- and loses at
+  // K = 4096: 37 vs 26 us)
+  if (!no_gemv && rows >= 1 && rows <= siu3r_gemm_pp::GV_ROWS && p.kpad >= 2048 && p.kpad <= siu3r_gemm_pp::GV_KMAX && p.k % 4 == 0 &&
+      ((int64_t)p.lda * esz) % 16 == 0 && ((uintptr_t)p.a % 16) == 0 && (p.sa * esz) % 16 == 0 && (p.sa_i * esz) % 16 == 0)
+    return 3;
+#endif
+  return 2;
+}
+
 // rows [p.m_main, p.m) (at most 32) of a dense problem
 int siu3r_gemm_skinny_launch(const siu3r_gemm_params& p, void* stream) {
   using namespace siu3r_gemm_pp;
@@ -265,14 +284,10 @@ int siu3r_gemm_skinny_launch(const siu3r_gemm_params& p, void* stream) {
   dim3 grid((p.n + 63) / 64, 1, p.batch > 0 ? p.batch : 1), block(512);
   hipStream_t s = (hipStream_t)stream;
   const bool lnf = p.ln_stats != nullptr;
+  const int path = siu3r_gemm_skinny_path(p);
+  if (path == 1) return 0;  // (the tile launch carried them)
 #ifndef SIU3R_PP_MINI
-  // at most four rows: the matrix-vector kernel (16-byte aligned A rows, K % 4 == 0, the rows fit its LDS)
-  const int rows = p.m - p.m_main, esz = x3 ? 4 : 2;
-  static const bool no_gemv = getenv("SIU3R_GEMM_NO_GEMV") != nullptr;
-  // (measured, tools/mb_skinny.py: the MFMA kernel above wins at K = 1024 -- 12.7 vs 14.7 us, both mostly fixed cost -- and loses at
-  // K = 4096: 37 vs 26 us)
-  if (!no_gemv && rows >= 1 && rows <= GV_ROWS && p.kpad >= 2048 && p.kpad <= GV_KMAX && p.k % 4 == 0 && ((int64_t)p.lda * esz) % 16 == 0 &&
-      ((uintptr_t)p.a % 16) == 0 && (p.sa * esz) % 16 == 0 && (p.sa_i * esz) % 16 == 0) {
+  if (path == 3) {
     if (x3 && lnf) hipLaunchKernelGGL((gemm_skinny_gemv_kernel<true, true>), grid, block, 0, s, p);
     else if (x3) hipLaunchKernelGGL((gemm_skinny_gemv_kernel<true, false>), grid, block, 0, s, p);
     else if (lnf) hipLaunchKernelGGL((gemm_skinny_gemv_kernel<false, true>), grid, block, 0, s, p);

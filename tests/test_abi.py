@@ -28,18 +28,18 @@ def test_library_exports_every_declared_symbol():
         assert hasattr(l, s), f"{s} declared in include/siu3r_hip.h but not exported"
         assert s in _lib.SIGNATURES, f"{s} has no ctypes signature"
     assert set(_lib.SIGNATURES) <= set(syms) | {"siu3r_last_error", "siu3r_abi_version"}
-    assert l.siu3r_abi_version() == _lib.ABI_VERSION == 11
+    assert l.siu3r_abi_version() == _lib.ABI_VERSION == 12
 
 
 def test_struct_layouts_match_c():
     """sizeof of the ctypes mirrors == sizeof of the C structs (compiled with the host compiler)."""
     from siu3r_amd import _lib
 
-    src = '#include <stdio.h>\n#include "siu3r_hip.h"\nint main(){printf("%zu %zu %zu %zu\\n", sizeof(siu3r_gemm_params), sizeof(siu3r_attn_params), sizeof(siu3r_raster_cam), sizeof(siu3r_attn_plan_t));return 0;}\n'
+    src = '#include <stdio.h>\n#include "siu3r_hip.h"\nint main(){printf("%zu %zu %zu %zu %zu\\n", sizeof(siu3r_gemm_params), sizeof(siu3r_attn_params), sizeof(siu3r_raster_cam), sizeof(siu3r_attn_plan_t), sizeof(siu3r_gemm_plan_t));return 0;}\n'
     exe = "/tmp/siu3r_sizeof"
     subprocess.run(["gcc", "-x", "c", "-", "-I", os.path.join(ROOT, "include"), "-o", exe], input=src.encode(), check=True)
     sizes = list(map(int, subprocess.run([exe], capture_output=True, check=True).stdout.split()))
-    assert sizes == [C.sizeof(_lib.GemmParams), C.sizeof(_lib.AttnParams), C.sizeof(_lib.RasterCam), C.sizeof(_lib.AttnPlan)], sizes
+    assert sizes == [C.sizeof(_lib.GemmParams), C.sizeof(_lib.AttnParams), C.sizeof(_lib.RasterCam), C.sizeof(_lib.AttnPlan), C.sizeof(_lib.GemmPlan)], sizes
 
 
 def test_oracle_raster_struct_matches():
@@ -241,6 +241,25 @@ def test_gemm_plan_consults_the_measured_table_then_the_model():
         assert with_ws.splitk >= 2, "few tiles and a long K: the model splits when it may"
     finally:
         _lib.check(lib.siu3r_gemm_tune(3, 0))
+
+
+def test_gemm_plan_reports_the_remainder_row_path():
+    """siu3r_gemm_plan_t.skinny_path (ABI 12): 0 without remainder rows, 1 when the tile launch carries them (kpad <= 2048 behind a
+    tiled part), 3 for the matrix-vector kernel (<= 4 rows, 2048 <= kpad <= 4096), 2 for the MFMA skinny kernel otherwise"""
+    from siu3r_amd import _lib
+
+    lib = _lib.lib()
+    try:
+        _lib.check(lib.siu3r_gemm_tune(3, 1))
+        _lib.check(lib.siu3r_gemm_tune(4, 1))  # remainder rows go to the skinny path whenever it is applicable
+        want = {(133, 264): (5, 1), (129, 2048): (1, 1), (129, 4096): (1, 3), (133, 4096): (5, 2), (17, 264): (17, 2), (4, 2048): (4, 3), (4, 1024): (4, 2), (161, 264): (0, 0)}
+        for (m, k), (rows, path) in want.items():
+            pl = _plan(m=m, n=128, k=k, tile_cfg=3, splitk=1)
+            assert (pl.skinny_rows, pl.skinny_path) == (rows, path), ((m, k), pl.skinny_rows, pl.skinny_path)
+        assert _plan(m=133, n=128, k=264, tile_cfg=-1).skinny_path == 0
+    finally:
+        _lib.check(lib.siu3r_gemm_tune(3, 0))
+        _lib.check(lib.siu3r_gemm_tune(4, 0))
 
 
 def test_gemm_plan_validates_like_the_launch():
