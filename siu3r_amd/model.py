@@ -13,6 +13,7 @@ precision = "bf16x3" : fp32 activations, every product as three bf16 MFMAs (hi*h
 """
 from __future__ import annotations
 
+import functools
 import math
 from typing import Dict, List, Optional, Sequence
 
@@ -494,15 +495,13 @@ class AsymmetricCroCo:
         decs = [[strip(t[:, v]) for t in dec["layers"]] for v in range(V)]
         return feats, all_feats, decs
 
-    def forward(self, context: dict, symmetrize_batch=False, return_views=False, after_encoder=None):
-        """reference signature backbone_croco.py:263-268 (+ after_encoder hook); context = {"image": [B,2,3,H,W], "intrinsics": [B,2,3,3]}."""
+    def forward(self, context: dict, symmetrize_batch=False, return_views=False):
+        """reference signature backbone_croco.py:263-268; context = {"image": [B,2,3,H,W], "intrinsics": [B,2,3,3]}."""
         assert not symmetrize_batch, "symmetrize_batch is a training-time option"
         images, K = context["image"], context["intrinsics"]
         B, V, _, H, W = images.shape
         assert V == 2, "AsymmetricCroCo is the two-view backbone; use AsymmetricCroCoMulti for more views"
         enc = self.encode(images, K)
-        if after_encoder is not None:
-            after_encoder()  # lets the caller fork the encoder-only consumers (ViT-Adapter branch) before the decoder
         dec = self.decode(enc)
         feats, all_feats, decs = self._assemble(enc, dec)
         shape = torch.tensor([[H, W]] * B)
@@ -1131,28 +1130,63 @@ class VideoMask2FormerForVideoSegmentation:
 # ==================================================================================================
 # whole model (model.py:31-389)
 # ==================================================================================================
-_PTS0_MAIN = os.environ.get("SIU3R_PTS0_MAIN", "0") == "1"
-_HEAD_MAP = os.environ.get("SIU3R_HEAD_MAP", "")
 _KV_PLANES = not os.environ.get("SIU3R_NO_KV_PLANES")  # A/B: k / v written pre-split by the q | k | v projections (bf16x3)
 _CONV_PLANES = not os.environ.get("SIU3R_NO_CONV_PLANES")  # A/B: pre-split planes between the convolutions of the paired DPT heads
 _DEC_QKVX = not os.environ.get("SIU3R_NO_DEC_QKVX")  # A/B: the decoder's self-attention q | k | v and the other side's cross-attention k | v as one launch
-_ADAPTER_LATE = int(os.environ.get("SIU3R_ADAPTER_LATE", "0"))  # A/B: run the ViT-Adapter interactions behind the encoder instead of beside it
 _HEAD_PAIRS = os.environ.get("SIU3R_NO_HEAD_PAIRS", "0") != "1"  # the two heads of a kind as grouped launches (V == 2, B == 1)
-_PAIR_MAP = os.environ.get("SIU3R_PAIR_MAP", "")  # A/B: streams of the (Gaussian pair, pts3d pair) chains, e.g. "0,m"
-_PTS0_OWN = os.environ.get("SIU3R_PTS0_OWN", "0") == "1"  # A/B: a fifth stream for the pts3d head of view 0 (needs GPU_MAX_HW_QUEUES >= 5 to overlap)
 _DEC_PER_LAYER = os.environ.get("SIU3R_DEC_PER_LAYER", "0") == "1"
-_PIPE_PTSR = int(os.environ.get("SIU3R_PIPE_PTSR", "0"))  # forward_async: the head stream (0 / 1) the pts3d head of views 1.. queues on
+
+# ---- the forward schedule: which stream every chain of the forward runs on, and the fork / join edges between
+# them, as data.  A step is (op, x, arg): ("run", x, stage) runs a stage on stream x, ("wait", x, y) makes x wait for what y holds so
+# far, ("after_seg", x, None) calls the hook behind Mask2Former on x.  SIU3RModel._run_stages interprets the steps.
+_MAIN, _SEG, _DEC, _H0, _H1 = range(5)  # the current stream | ViT-Adapter + Mask2Former | the decoder's other side | two head streams
+
+
+@functools.lru_cache(maxsize=None)
+def _schedule(paired: bool, merged: bool, dec_depth: int, pipelined: bool):
+    """(the steps of one forward in enqueue order, the stream of the tail).  paired: both heads of a kind as one chain; merged: both
+    decoder sides in grouped launches; pipelined (forward_async): the current stream carries encoder -> decoder only."""
+    # the encoder on the current stream, the ViT-Adapter beside it: the spatial prior module needs only the image, interaction k only
+    # the tokens of encoder block ADAPTER_IDX[k].  Mask2Former and the panoptic device stage then overlap the decoder and the heads
+    steps = [("run", _MAIN, "enc_begin"), ("wait", _SEG, _MAIN), ("run", _SEG, "spm")]
+    for k in range(len(ADAPTER_IDX)):
+        steps += [("run", _MAIN, f"enc{k}"), ("wait", _SEG, _MAIN), ("run", _SEG, f"int{k}")]
+    steps += [("run", _SEG, "seg"), ("after_seg", _SEG, None), ("run", _MAIN, "dec_pre")]
+    if merged:
+        steps += [("run", _MAIN, f"dec{i}") for i in range(dec_depth)] if _DEC_PER_LAYER else [("run", _MAIN, "dec_all")]
+    for i in range(0 if merged else dec_depth):  # per layer, view 0 and the other views are independent chains, joined after every layer
+        steps += [("wait", _DEC, _MAIN), ("run", _MAIN, f"decA{i}"), ("run", _DEC, f"decB{i}"), ("wait", _MAIN, _DEC)]
+    # every head chain reads the decoder's outputs.  (_SEG: the pts3d head of view 0 rides behind Mask2Former, which ends soon after
+    # the heads start: it then overlaps the other three chains instead of running alone after them)
+    steps += [("run", _MAIN, "dec_post"), ("wait", _H0, _MAIN), ("wait", _H1, _MAIN), ("wait", _SEG, _MAIN)]
+    # pipelined: nothing behind the decoder stays on the current stream, where the caller enqueues the next step's encoder
+    if paired:
+        steps += [("run", _H0, "gs"), ("run", _H1 if pipelined else _MAIN, "pts")]
+    else:  # three chains of about equal length: each Gaussian head on its own stream, the pts3d head of the other views on the current one
+        steps += [("run", _H0, "gs0"), ("run", _H1, "gsr"), ("run", _H0 if pipelined else _MAIN, "ptsr"), ("run", _SEG, "pts0")]
+    tail = _H1 if pipelined else _MAIN
+    steps += [("wait", tail, _H0), ("wait", tail, _H1), ("wait", tail, _SEG), ("wait", tail, _SEG), ("run", tail, "tail")]
+    return tuple(steps), tail
+
+
+_PANOPTIC_TABLES = ("tab", "probs", "kept_idx", "acc_list", "p256", "seg", "sem", "ins")  # what begin_panoptic() allocates on the segmentation stream
 
 
 class _PendingForward:
-    """Handle of SIU3RModel.forward_async(): the device side of the step is enqueued; result() does the host half (once)."""
+    """Handle of SIU3RModel.forward_async(): the device side of the step is enqueued; result() does the host half (once).  Carries the
+    step's state from _submit to SIU3RModel._after_seg (enqueue time, on the segmentation stream) and SIU3RModel._finish (result())."""
 
-    def __init__(self, finish):
-        self._finish, self._out, self.done = finish, None, False
+    def __init__(self, model, st, caller, host_slot, eager, replayed, lift, return_intermediates):
+        self._model, self._out, self.done = model, None, False
+        self.st, self.caller, self.host_slot, self.eager, self.replayed = st, caller, host_slot, eager, replayed
+        self.lift, self.return_intermediates = lift, return_intermediates
+        self.seg_out = self.pend = self.gaussians = None  # the segmentation output, the pending panoptic tables, the Gaussian fields
+        self.tail_stream = caller  # the stream every chain of the step was joined into
 
     def result(self):
         if not self.done:
-            self._out, self.done, self._finish = self._finish(), True, None
+            self._out, self.done = self._model._finish(self), True
+            self._model = self.st = self.seg_out = self.pend = self.gaussians = None
         return self._out
 
 
@@ -1249,110 +1283,112 @@ class SIU3RModel:
         K = context_views_intrinsics.to(ctx.dev)
         B, V, _, H, W = images.shape
         key = (B, V, H, W, images.dtype, K.dtype)
+        # the mode: eager | the first call of a shape (eager too, and sizes the split-K workspaces) | replay of the slot's chain graphs
         eager = (not self.use_graph) or return_intermediates or ops.kernel_timer_active() or torch.cuda.is_current_stream_capturing()
         ent = None if eager else self._graphs.get(key)
+        replayed = ent is not None
         caller = torch.cuda.current_stream()
         # slot None (forward()): state slot 0, and the chains are joined back into the caller's stream before the tail.  slot s
         # (forward_async): state slot s, and the caller's stream carries ONLY encoder -> decoder: the heads, the joins and the tail stay
         # on the side streams, so that the next step's encoder (enqueued on the caller's stream right behind this step's decoder) starts
-        # while this step's heads run; result() joins.  (One set of streams for all slots on purpose: this runtime multiplexes streams
-        # onto 4 hardware queues in order of first use, and a second set of streams ended up sharing queues with the first -- slot 1's
-        # encoder then simply queued behind slot 0's tail; with 8 queues everything overlapped and the step got 10-35 % SLOWER.)
+        # while this step's heads run; result() joins.  One set of streams for all slots on purpose: a second set would share the four
+        # hardware queues with the first.
         sidx = 0 if slot is None else slot
         pipelined = slot is not None and ctx.concurrent
-        pp_state = {"tail_stream": caller}
-
-        def make_after_seg(st_, copy_out):
-            # runs on the segmentation stream right behind Mask2Former: the panoptic device stage and the asynchronous read-back of its
-            # tables overlap the heads; the host picks the tables up (an event) after everything is enqueued
-            def after_seg():
-                seg_o = VideoMask2FormerForVideoSegmentationOutput(st_.seg) if copy_out else st_.seg
-                if copy_out:  # the logits leave the graphs' private memory, which the next replay overwrites
-                    for k_ in ("class_queries_logits", "masks_queries_logits"):
-                        seg_o[k_] = seg_o[k_].clone()
-                        seg_o[k_].record_stream(caller)
-                pend = self.processor.begin_panoptic(seg_o, threshold=self.seg_threshold, target_sizes=[(H, W)] * B,
-                                                     label_ids_to_fuse=self.label_ids_to_fuse, host_slot=sidx)
-                for k_ in ("tab", "probs", "kept_idx", "acc_list", "p256", "seg", "sem", "ins"):
-                    pend[k_].record_stream(caller)  # allocated on the segmentation stream, read on the caller's
-                pp_state["seg_out"], pp_state["pend"] = seg_o, pend
-            return after_seg
-
-        if eager or ent is None:
-            need = {}
-            if not eager:
-                # first call of this shape: eager (packs weights, fills caches) -- and measures the split-K workspace every chain asks for
-                ent = self._graphs[key] = {"graphs": None, "st": None, "slots": {}, "need": need}
-            st = _Run(images, K)
-            st.want_f1 = bool(return_intermediates)
-
-            def run_eager(name, fn):
-                if eager:
-                    return fn()
-                with ops.splitk_meter() as m:
-                    fn()
-                need[name] = m
-
-            self._run_stages(st, run_eager, make_after_seg(st, False))
-        else:
+        # the run state: the slot's static buffers and chain graphs, or a fresh _Run
+        if replayed:
             sl = ent["slots"].get(sidx)
             if sl is None:
                 sl = ent["slots"][sidx] = self._capture_slot(ent, key, images, K)
                 if sidx == 0:
                     ent["graphs"], ent["st"] = sl["graphs"], sl["st"]  # (tools/ read the first slot through these)
             st = sl["st"]
+        else:
+            st = _Run(images, K)
+            st.want_f1 = bool(return_intermediates)
+        h = _PendingForward(self, st, caller, sidx, eager, replayed, enable_query_class_logit_lift, return_intermediates)
+        after_seg = functools.partial(self._after_seg, h)
+        # enqueue
+        if replayed:
             if sl.get("done") is not None:
                 caller.wait_event(sl["done"])  # the slot's previous step (a no-op when its result() ran on this stream, as it normally has)
             st.images.copy_(images, non_blocking=True)
             st.K.copy_(K, non_blocking=True)
-            tl = self._timeline
-
-            def replay(name, fn):
-                if tl is not None:  # tools/timeline.py: stage start / end events on the stage's own stream
-                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    e0.record()
-                fn() if name == "tail" else sl["graphs"][name].replay()
-                if tl is not None:
-                    e1.record()
-                    tl.append((name, e0, e1))
-
-            pp_state["tail_stream"] = self._run_stages(st, replay, make_after_seg(st, True), pipelined=pipelined)
+            h.tail_stream = self._run_stages(st, functools.partial(self._replay_stage, sl), after_seg, pipelined=pipelined)
             if pipelined:
                 sl["done"] = torch.cuda.Event()
-                sl["done"].record(pp_state["tail_stream"])
-        # the Gaussians come from the eager tail (fresh memory)
-        gaussians = st.gaussians
-        tail_stream = pp_state["tail_stream"]
+                sl["done"].record(h.tail_stream)
+        elif eager:
+            self._run_stages(st, lambda name, fn: fn(), after_seg)
+        else:
+            # first call of this shape: eager (packs weights, fills caches) -- and measures the split-K workspace every chain asks for
+            ent = self._graphs[key] = {"graphs": None, "st": None, "slots": {}, "need": {}}
+            self._run_stages(st, functools.partial(self._meter_stage, ent["need"]), after_seg)
+        h.gaussians = st.gaussians  # from the eager tail: fresh memory
+        return h
 
-        def finish():
-            cur = torch.cuda.current_stream()
-            if tail_stream is not cur:
-                cur.wait_stream(tail_stream)  # the Gaussian fields (pipelined: the tail ran on a head stream, every chain joined into it)
-                for _, v_ in gaussians.items():
-                    if isinstance(v_, torch.Tensor):
-                        v_.record_stream(cur)
-            seg_out = pp_state["seg_out"]
-            if cur is not caller:
-                for k_ in ("tab", "probs", "kept_idx", "acc_list", "p256", "seg", "sem", "ins"):
-                    pp_state["pend"][k_].record_stream(cur)
-            results = self.processor.finish_panoptic(pp_state["pend"])
-            if not eager:
-                # the channel-last logits / mask features / memory levels live in the graphs' private memory, which the next replay
-                # overwrites: they served the post-process above and do not leave with the result
-                for k_ in ("_masks_channel_last", "_mask_features", "_ms"):
-                    seg_out.pop(k_, None)
-            g_, masks, infos, qcl, qscores = pp.post_process_gaussians(gaussians, results, B, V, H, W, enable_query_class_logit_lift)
-            if return_intermediates:
-                _, _, decs = self.backbone._assemble(st.enc, st.dec)
-                all1 = [t[:, 0, :-1] for t in st.enc["av"]]
-                all2 = [t[:, 1, :-1] for t in st.enc["av"]]
-                self._last = dict(dec1=decs[0], dec2=decs[1], decs=decs, all_feat1=all1, all_feat2=all2, ms=st.ms, lat1=st.adapter["lat1"], pts1=st.pts[0],
-                                  pts2=st.pts[1], gs_raw1=st.gs[0].reshape(B, H, W, -1), gs_raw2=st.gs[1].reshape(-1, H, W, st.gs[1].shape[-1]), seg_out=st.seg)
-            if enable_query_class_logit_lift:
-                return g_, seg_out, masks, infos, qscores
-            return g_, seg_out, masks, infos
+    @staticmethod
+    def _meter_stage(need, name, fn):
+        with ops.splitk_meter() as m:
+            fn()
+        need[name] = m
 
-        return _PendingForward(finish)
+    def _replay_stage(self, sl, name, fn):
+        tl = self._timeline
+        if tl is not None:  # tools/timeline.py: stage start / end events on the stage's own stream
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+        fn() if name == "tail" else sl["graphs"][name].replay()
+        if tl is not None:
+            e1.record()
+            tl.append((name, e0, e1))
+
+    def _after_seg(self, h):
+        """Runs on the segmentation stream right behind Mask2Former: the panoptic device stage and the asynchronous read-back of its
+        tables overlap the heads; the host picks the tables up (an event) in _finish, after everything is enqueued."""
+        st = h.st
+        B, _, _, H, W = st.images.shape
+        seg_o = st.seg
+        if h.replayed:  # the logits leave the graphs' private memory, which the next replay overwrites
+            seg_o = VideoMask2FormerForVideoSegmentationOutput(st.seg)
+            for k_ in ("class_queries_logits", "masks_queries_logits"):
+                seg_o[k_] = seg_o[k_].clone()
+                seg_o[k_].record_stream(h.caller)
+        pend = self.processor.begin_panoptic(seg_o, threshold=self.seg_threshold, target_sizes=[(H, W)] * B,
+                                             label_ids_to_fuse=self.label_ids_to_fuse, host_slot=h.host_slot)
+        for k_ in _PANOPTIC_TABLES:
+            pend[k_].record_stream(h.caller)  # allocated on the segmentation stream, read on the caller's
+        h.seg_out, h.pend = seg_o, pend
+
+    def _finish(self, h):
+        """The host half of a step (result()): joins the step into the current stream, waits for the panoptic tables, builds the result."""
+        st, seg_out, gaussians = h.st, h.seg_out, h.gaussians
+        B, V, _, H, W = st.images.shape
+        cur = torch.cuda.current_stream()
+        if h.tail_stream is not cur:
+            cur.wait_stream(h.tail_stream)  # the Gaussian fields (pipelined: the tail ran on a head stream, every chain joined into it)
+            for _, v_ in gaussians.items():
+                if isinstance(v_, torch.Tensor):
+                    v_.record_stream(cur)
+        if cur is not h.caller:
+            for k_ in _PANOPTIC_TABLES:
+                h.pend[k_].record_stream(cur)
+        results = self.processor.finish_panoptic(h.pend)
+        if not h.eager:
+            # the channel-last logits / mask features / memory levels live in the graphs' private memory, which the next replay
+            # overwrites: they served the post-process above and do not leave with the result
+            for k_ in ("_masks_channel_last", "_mask_features", "_ms"):
+                seg_out.pop(k_, None)
+        g_, masks, infos, qcl, qscores = pp.post_process_gaussians(gaussians, results, B, V, H, W, h.lift)
+        if h.return_intermediates:
+            _, _, decs = self.backbone._assemble(st.enc, st.dec)
+            all1 = [t[:, 0, :-1] for t in st.enc["av"]]
+            all2 = [t[:, 1, :-1] for t in st.enc["av"]]
+            self._last = dict(dec1=decs[0], dec2=decs[1], decs=decs, all_feat1=all1, all_feat2=all2, ms=st.ms, lat1=st.adapter["lat1"], pts1=st.pts[0],
+                              pts2=st.pts[1], gs_raw1=st.gs[0].reshape(B, H, W, -1), gs_raw2=st.gs[1].reshape(-1, H, W, st.gs[1].shape[-1]), seg_out=st.seg)
+        if h.lift:
+            return g_, seg_out, masks, infos, qscores
+        return g_, seg_out, masks, infos
 
     def _capture_slot(self, ent, key, images, K):
         """Static buffers + one HIP graph per chain for one slot of this shape.  The chain's split-K workspace is its own (the chain
@@ -1438,103 +1474,31 @@ class SIU3RModel:
         return self._ctx.fold and st.images.shape[1] == 2
 
     def _run_stages(self, st, run, after_seg=None, pipelined=False):
-        """Enqueue the stages with their fork/join edges.  run(name, fn) either calls fn (eager) or replays its graph.  after_seg(): enqueued
-        on the segmentation stream right behind Mask2Former (the device half of the panoptic post-process).  Returns the stream the
-        tail ran on (every chain is joined into it).  pipelined (forward_async): the current stream carries only encoder -> decoder;
-        the pts3d head of the other views, the joins and the tail go to the head streams, so that whatever the caller enqueues next on
-        the current stream (the next step's encoder) is not ordered behind this step's heads."""
+        """Enqueue the stages with their fork/join edges: the steps of _schedule(), one after the other.  run(name, fn) either calls fn
+        (eager) or replays its graph.  after_seg(): enqueued on the segmentation stream right behind Mask2Former (the device half of the
+        panoptic post-process).  Returns the stream the tail ran on (every chain is joined into it).  pipelined (forward_async): the
+        current stream carries only encoder -> decoder; the pts3d head of the other views, the joins and the tail go to the head streams,
+        so that whatever the caller enqueues next on the current stream (the next step's encoder) is not ordered behind this step's heads.
+        tests/test_forward_schedule.py pins the enqueued sequence, edge for edge."""
         ctx = self._ctx
         stages = dict(self._stages(st))
         main = torch.cuda.current_stream()
-        par = ctx.concurrent
-        # encoder on the current stream; the ViT-Adapter rides beside it on its own stream: the spatial prior module needs
-        # only the image, interaction k only the tokens of encoder block ADAPTER_IDX[k].  The rest of the segmentation
-        # branch (adapter output maps, Mask2Former) then overlaps the decoder and the heads
-        run("enc_begin", stages["enc_begin"])
-        seg_stream = ctx.side_stream(1) if par else main
-        if par:
-            seg_stream.wait_stream(main)
-        late = _ADAPTER_LATE if par else 0  # A/B: 1 = every interaction behind the whole encoder, 2 = the spatial prior module too
-        if late < 2:
-            with torch.cuda.stream(seg_stream):
-                run("spm", stages["spm"])
-        for k in range(len(ADAPTER_IDX)):
-            run(f"enc{k}", stages[f"enc{k}"])
-            if late:
-                continue
-            if par:
-                seg_stream.wait_stream(main)
-            with torch.cuda.stream(seg_stream):
-                run(f"int{k}", stages[f"int{k}"])
-        if late:
-            seg_stream.wait_stream(main)
-            with torch.cuda.stream(seg_stream):
-                if late >= 2:
-                    run("spm", stages["spm"])
-                for k in range(len(ADAPTER_IDX)):
-                    run(f"int{k}", stages[f"int{k}"])
-        with torch.cuda.stream(seg_stream):
-            run("seg", stages["seg"])
-            if after_seg is not None:
-                after_seg()
-        # decoder: per layer, view 0 and the other views are independent chains (joined after every layer)
-        run("dec_pre", stages["dec_pre"])
-        dside = ctx.side_stream(0) if par else main
-        if "dec_all" in stages:
-            run("dec_all", stages["dec_all"])
-        for i in range(self.backbone.dec_depth):
-            if self._merged_decoder(st):  # both sides of the pair in grouped launches on the main stream
-                if "dec_all" not in stages:
-                    run(f"dec{i}", stages[f"dec{i}"])
-                continue
-            if par:
-                dside.wait_stream(main)
-            run(f"decA{i}", stages[f"decA{i}"])
-            with torch.cuda.stream(dside):
-                run(f"decB{i}", stages[f"decB{i}"])
-            if par:
-                main.wait_stream(dside)
-        run("dec_post", stages["dec_post"])
-        # the two Gaussian heads (5.8 ms each in bf16x3) on their own streams; the two pts3d heads (3.3 + 1.7 ms) back to back on the main
-        # stream: three chains of about equal length.  (A fourth stream for pts0 shares a hardware queue with one of the others on this
-        # runtime -- it then ran alone AFTER the Gaussian heads; with GPU_MAX_HW_QUEUES=8 it overlaps, but the extra concurrency slows
-        # the encoder / decoder critical path by more than it saves: 25.3 -> 31.3 ms.)
-        hs = [ctx.side_stream(2 + i) if par else main for i in range(2)]
-        for s_ in hs:
-            if s_ is not main:
-                s_.wait_stream(main)
-        # pts0 rides on the segmentation stream, behind Mask2Former: that chain ends ~2.5 ms after the heads start, and the head of view 0
-        # then overlaps the other three instead of running alone after them (21.8 -> 20.9 ms body at B = 1; SIU3R_PTS0_MAIN=1 restores
-        # the two pts3d heads back to back on the main stream)
-        pts0_stream = (ctx.side_stream(4) if _PTS0_OWN else seg_stream) if (par and not _PTS0_MAIN) else main
-        if pts0_stream is not main:
-            pts0_stream.wait_stream(main)  # the decoder's outputs
-        pipelined = pipelined and par
-        ptsr_stream = hs[_PIPE_PTSR] if pipelined else main  # pipelined: behind one of the Gaussian heads instead of on the encoder's stream
-        placement = list(zip(("gs0", "gsr", "ptsr", "pts0"), hs + [ptsr_stream, pts0_stream]))
-        if "gs" in stages:  # paired heads: two chains (both Gaussian heads | both pts3d heads)
-            pick = {"0": hs[0], "1": hs[1], "m": main, "s": seg_stream}
-            k_gs, k_pts = (_PAIR_MAP.split(",") if (_PAIR_MAP and par) else ("0", "1" if pipelined else "m"))
-            placement = [("gs", pick[k_gs] if par else main), ("pts", pick[k_pts] if par else main)]
-            for _, s_ in placement:
-                if s_ is seg_stream and par:
-                    seg_stream.wait_stream(main)
-        elif _HEAD_MAP and par:  # A/B: SIU3R_HEAD_MAP="0,1,m,s" = stream of gs0, gsr, ptsr, pts0 (0 / 1 head streams, m main, s segmentation), in launch order
-            pick = {"0": hs[0], "1": hs[1], "m": main, "s": seg_stream}
-            placement = [(n_, pick[k_]) for n_, k_ in zip(("gs0", "gsr", "ptsr", "pts0"), _HEAD_MAP.split(","))]
-            for _, s_ in placement:
-                if s_ is seg_stream:
-                    seg_stream.wait_stream(main)
-        for name, s_ in placement:
-            with torch.cuda.stream(s_):
-                run(name, stages[name])
-        tail_stream = hs[1] if pipelined else main
-        for s_ in hs + [seg_stream, pts0_stream]:
-            if s_ is not tail_stream:
-                tail_stream.wait_stream(s_)
-        with torch.cuda.stream(tail_stream):
-            run("tail", stages["tail"])
-        return tail_stream
+        # _MAIN, _SEG, _DEC, _H0, _H1.  Not concurrent: all five are the current stream, and every wait falls away (below)
+        streams = (main, ctx.side_stream(1), ctx.side_stream(0), ctx.side_stream(2), ctx.side_stream(3)) if ctx.concurrent else (main,) * 5
+        steps, tail = _schedule(self._paired_heads(st), self._merged_decoder(st), self.backbone.dec_depth, bool(pipelined))
+        for op, x, arg in steps:
+            x = streams[x]
+            if op == "wait":
+                if x is not streams[arg]:  # a wait between a stream and itself is dropped
+                    x.wait_stream(streams[arg])
+            elif op == "after_seg" and after_seg is None:
+                pass
+            elif x is main:  # already the current stream
+                run(arg, stages[arg]) if op == "run" else after_seg()
+            else:
+                with torch.cuda.stream(x):
+                    run(arg, stages[arg]) if op == "run" else after_seg()
+        return streams[tail]
 
     def _s_encode_begin(self, st):
         ctx = self._ctx
