@@ -115,7 +115,7 @@ def render_cuda(extrinsics, intrinsics, near, far, image_shape, background_color
         delta = None if cam_rot_delta is None else torch.cat((cam_trans_delta[i0:i1], cam_rot_delta[i0:i1]), dim=-1).float()
         out = raster.rasterize_views_k2(cams, gaussian_means[i0], gaussian_covariances[i0], sh_i if planar else sh_i.permute(0, 2, 1).contiguous(),
                                         gaussian_opacities[i0], want_n_touched=return_aux, entry_capacity=entry_capacity, sh_planar=planar,
-                                        check_overflow=check_overflow, pose_c2w=pose, pose_delta=delta, **({} if density_stats is None else {"density_stats": density_stats}))
+                                        check_overflow=check_overflow, pose_c2w=pose, pose_delta=delta, density_stats=density_stats)
         images.append(out["image"])
         depths.append(out["depth"])
         aux.append(out)

@@ -109,69 +109,81 @@ class RasterOverflow(RuntimeError):
         self.call_id = call_id
 
 
-class _State(dict):
-    """Buffers of one rasterizer call (V views).  The per-tile Gaussian lists are not needed to render an RGB view; they are
-    produced on first access of "tile_start" / "ids" (tests, exports).  "D" / "Gv" / "E" read the device-side totals."""
+class RasterState:
+    """Buffers of one rasterizer call (V views); __slots__ is everything a call's state can hold (None until set).  The per-tile Gaussian
+    lists are not needed to render an RGB view: the properties tile_start_all / ids_all / cap_d (tile_start / ids: view 0) build them on
+    first use.  Gv / D / E read the device-side totals of view 0.  state["name"] reads the attribute `name`; nothing is written that way."""
+    __slots__ = ("V", "G", "W", "H", "T", "geo", "cams", "cams_dev",  # sizes, geometry(W, H, G), the host RasterCam array and its device blocks
+                 "rec", "radii", "rect", "tiles_touched_all", "keys", "keys_b", "sorted_ids", "ids_b",  # per (view, Gaussian)
+                 "stats_dev", "bin_start", "entries", "cap_e",  # [V,4] i64 device counters (stats(): their host copy), the coarse bins
+                 "pose_dev",  # the two device pose tensors of a "dp" / "c2w" call: like feat_ws kept here because launches read them asynchronously
+                 "defer", "cap_d_hint",  # the caller checks for overflow later: nothing synchronises; pair capacity the lists start from
+                 "feat_ws", "feat_ws_lists",  # workspace of the N-channel matrix-core composite, and whether it holds the per-quadrant lists
+                 "_stats_host", "_tl")  # _tl: (tile_start_all [V,T+2], ids_all [V,cap_d], cap_d) once _lists() ran
+
+    def __init__(self, **fields):
+        for k in self.__slots__:
+            setattr(self, k, fields.pop(k, None))
+        assert not fields, f"not a field of RasterState: {sorted(fields)}"
+
+    def __getitem__(self, k):  # read-only (there is no __setitem__), and only the public fields and properties: _KEYS below
+        if k not in self._KEYS:
+            raise KeyError(k)
+        return getattr(self, k)
 
     def stats(self) -> torch.Tensor:
-        if not dict.__contains__(self, "stats_host"):
-            dict.__setitem__(self, "stats_host", dict.__getitem__(self, "stats").cpu())
-        return dict.__getitem__(self, "stats_host")
+        if self._stats_host is None:
+            self._stats_host = self.stats_dev.cpu()
+        return self._stats_host
 
     def totals(self, k: int) -> List[int]:
         return [int(x) for x in self.stats()[:, k].tolist()]
 
     def verify(self):
         """Raise when a capacity-bounded buffer overflowed (only needed by callers that passed check=False)."""
-        st = self.stats()
-        e_max, cap_e = int(st[:, 2].max()), dict.__getitem__(self, "cap_e")
-        if e_max > cap_e:
-            raise RasterOverflow(f"rasterizer coarse-bin entries overflowed: E = {e_max} > entry_capacity {cap_e} (pass entry_capacity >= {e_max})")
+        e_max = int(self.stats()[:, 2].max())
+        if e_max > self.cap_e:
+            raise RasterOverflow(f"rasterizer coarse-bin entries overflowed: E = {e_max} > entry_capacity {self.cap_e} (pass entry_capacity >= {e_max})")
         # the materialised (tile, Gaussian) pair lists of the N-channel path (tl_scan sets flag bit 1 when a view's pairs exceed
         # pair_capacity: far splats would silently be missing from tiles).  Deferred callers (check_overflow=False) must call verify().
-        if dict.__contains__(self, "tile_start_all"):
-            T, cap_d = dict.__getitem__(self, "T"), dict.__getitem__(self, "cap_d")
-            d_max = int(dict.__getitem__(self, "tile_start_all")[:, T + 1].max())
+        if self._tl is not None:  # (only when they were built: verify() never builds them)
+            tstart, _, cap_d = self._tl
+            d_max = int(tstart[:, self.T + 1].max())
             if d_max > cap_d:  # (the sticky flag bit of an earlier, repeated attempt is not consulted: the scan's own total is)
                 raise RasterOverflow(f"rasterizer tile-pair lists overflowed: D = {d_max} > pair_capacity {cap_d} (pass pair_capacity >= {d_max})")
 
-    def _lists(self):
-        if not dict.__contains__(self, "ids"):
-            V, T = dict.__getitem__(self, "V"), dict.__getitem__(self, "T")
-            dev = dict.__getitem__(self, "stats").device
-            hint_key = ("pairs", dict.__getitem__(self, "G"), V, dict.__getitem__(self, "W"), dict.__getitem__(self, "H"))
-            cap_d = dict.__getitem__(self, "cap_d_hint") or max(1, max(self.totals(1)))
+    def _lists(self) -> tuple:
+        if self._tl is None:
+            V, T, dev = self.V, self.T, self.stats_dev.device
+            hint_key = ("pairs", self.G, V, self.W, self.H)
+            cap_d = self.cap_d_hint or max(1, max(self.totals(1)))
             cap_d = max(cap_d, _CAPACITY_HINTS.get(hint_key, 0))
             while True:
                 tcount = torch.empty((V, T), dtype=torch.int32, device=dev)
                 tstart = torch.empty((V, T + 2), dtype=torch.int32, device=dev)
                 ids = torch.empty((V, cap_d), dtype=torch.int32, device=dev)
-                check(_lib.lib().siu3r_raster_tile_lists(dict.__getitem__(self, "cams"), V, _p(dict.__getitem__(self, "bin_start")),
-                                                         _p(dict.__getitem__(self, "entries")), dict.__getitem__(self, "cap_e"), _p(tcount),
-                                                         _p(tstart), _p(ids), cap_d, _p(dict.__getitem__(self, "stats")), _stream()))
-                if dict.__getitem__(self, "defer"):
+                check(_lib.lib().siu3r_raster_tile_lists(self.cams, V, _p(self.bin_start), _p(self.entries), self.cap_e, _p(tcount), _p(tstart), _p(ids),
+                                                         cap_d, _p(self.stats_dev), _stream()))
+                if self.defer:
                     break
                 d_max = int(tstart[:, T + 1].max())
                 if d_max <= cap_d:
                     break
                 cap_d = d_max  # the bound was too small: repeat with the exact pair count
                 _remember(*hint_key, d_max)
-            dict.__setitem__(self, "cap_d", cap_d)
-            dict.__setitem__(self, "tile_start_all", tstart)
-            dict.__setitem__(self, "ids_all", ids)
-            dict.__setitem__(self, "ids", ids[0])
-            dict.__setitem__(self, "tile_start", tstart[0])
+            self._tl = (tstart, ids, cap_d)
+        return self._tl
 
-    def __getitem__(self, k):
-        if k in ("ids", "tile_start", "ids_all", "tile_start_all", "cap_d"):
-            self._lists()
-        elif k == "D":
-            return self.totals(1)[0]
-        elif k == "Gv":
-            return self.totals(0)[0]
-        elif k == "E":
-            return self.totals(2)[0]
-        return dict.__getitem__(self, k)
+    tile_start_all = property(lambda self: self._lists()[0])
+    ids_all = property(lambda self: self._lists()[1])
+    cap_d = property(lambda self: self._lists()[2])
+    tile_start = property(lambda self: self._lists()[0][0])
+    ids = property(lambda self: self._lists()[1][0])
+    tiles_touched = property(lambda self: self.tiles_touched_all[0])
+    Gv = property(lambda self: self.totals(0)[0])
+    D = property(lambda self: self.totals(1)[0])
+    E = property(lambda self: self.totals(2)[0])
+    _KEYS = frozenset(__slots__[:-2] + ("tile_start_all", "ids_all", "cap_d", "tile_start", "ids", "tiles_touched", "Gv", "D", "E"))
 
 
 def _cam_array(cams: Sequence[RasterCam]):
@@ -200,46 +212,53 @@ def _pose_dev(pose_dev, V, dev):
     return vm, Ks
 
 
+_Pose = collections.namedtuple("_Pose", "kind a b t_scale")
+_HOST_POSE = _Pose("host", None, None, 1.0)
+
+
+def _pose(V, dev, pose_dev=None, pose_c2w=None) -> _Pose:
+    """Where the projection takes a call's pose from, made once at the entry point.  Neither keyword: kind "host", the camera blocks carry it.
+    pose_dev = (viewmats [V,4,4] world->camera, Ks [V,3,3] pixel units) as DEVICE tensors (gsplat family): kind "dp", the kernels take the pose
+    from a, b (siu3r_raster_project_dp), `cams` only carries frame size, planes and thresholds.  pose_c2w = (extrinsics [V,4,4] camera-to-world,
+    normalised intrinsics [V,3,3], t_scale): DEVICE tensors + a float, either family, kind "c2w" (SplattingCUDA.forward; siu3r_raster_project_c2w)."""
+    if pose_c2w is not None:
+        return _Pose("c2w", *_pose_dev(pose_c2w[:2], V, dev), float(pose_c2w[2]))
+    if pose_dev is not None:
+        return _Pose("dp", *_pose_dev(pose_dev, V, dev), 1.0)
+    return _HOST_POSE
+
+
 def _project_sort_bin(cams: Sequence[RasterCam], means, cov, opac, colors, channels, entry_capacity=None, check_overflow=True,
-                      sh_planar=False, pose_dev=None, pose_c2w=None) -> _State:
-    """pose_dev: None, or (viewmats [V,4,4] world->camera, Ks [V,3,3] pixel units) as DEVICE tensors (gsplat family): the kernels take the
-    pose from them (siu3r_raster_project_dp) and `cams` only carries frame size, planes and thresholds.
-    pose_c2w: None, or (extrinsics [V,4,4] camera-to-world, normalised intrinsics [V,3,3], t_scale) as DEVICE tensors + a float, either
-    family: what SplattingCUDA.forward receives; inverse / fov / projection are derived on the device (siu3r_raster_project_c2w)."""
+                      sh_planar=False, pose: _Pose = _HOST_POSE) -> RasterState:
     V, G, dev = len(cams), means.shape[0], means.device
     arr = _cam_array(cams)
-    geo = geometry(cams[0].width, cams[0].height, G)
+    W, H = cams[0].width, cams[0].height
+    geo = geometry(W, H, G)
     f = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)
     i32 = lambda *s: torch.empty(s, dtype=torch.int32, device=dev)
-    cap_e = int(entry_capacity) if entry_capacity else _hinted("entries", G, V, cams[0].width, cams[0].height, default_entry_capacity(G))
-    st = _State(V=V, G=G, W=cams[0].width, H=cams[0].height, T=geo["T"], geo=geo, cams=arr, cams_dev=torch.empty((V * geo["cam_bytes"],), dtype=torch.uint8, device=dev),
-                rec=f(V, G, 12), radii=i32(V, G, 2), rect=i32(V, G, 4), tiles_touched_all=i32(V, G), keys=i32(V, G), keys_b=i32(V, G), sorted_ids=i32(V, G), ids_b=i32(V, G),
-                stats=torch.empty((V, 4), dtype=torch.int64, device=dev), defer=not check_overflow, cap_d_hint=None)
-    st["tiles_touched"] = st["tiles_touched_all"][0]
+    cap_e = int(entry_capacity) if entry_capacity else _hinted("entries", G, V, W, H, default_entry_capacity(G))
+    st = RasterState(V=V, G=G, W=W, H=H, T=geo["T"], geo=geo, cams=arr, cams_dev=torch.empty((V * geo["cam_bytes"],), dtype=torch.uint8, device=dev),
+                     rec=f(V, G, 12), radii=i32(V, G, 2), rect=i32(V, G, 4), tiles_touched_all=i32(V, G), keys=i32(V, G), keys_b=i32(V, G), sorted_ids=i32(V, G),
+                     ids_b=i32(V, G), stats_dev=torch.empty((V, 4), dtype=torch.int64, device=dev), defer=not check_overflow, cap_e=cap_e)
     lib = _lib.lib()
-    if pose_c2w is not None:
-        e_, k_, t_scale = pose_c2w
-        e_, k_ = st["pose_dev"] = _pose_dev((e_, k_), V, dev)  # (kept with the state: the launches read them asynchronously)
-        check(lib.siu3r_raster_project_c2w(arr, V, _p(st["cams_dev"]), _p(e_), _p(k_), float(t_scale), G, _p(means), _p(cov), _cov_stride(cov), _p(opac),
-                                           _p(colors), channels, int(bool(sh_planar)), _p(st["rec"]), _p(st["radii"]), _p(st["rect"]),
-                                           _p(st["tiles_touched_all"]), _p(st["keys"]), _p(st["stats"]), _stream()))
-    elif pose_dev is None:
-        check(lib.siu3r_raster_project(arr, V, _p(st["cams_dev"]), G, _p(means), _p(cov), _cov_stride(cov), _p(opac), _p(colors), channels,
-                                       int(bool(sh_planar)), _p(st["rec"]), _p(st["radii"]), _p(st["rect"]), _p(st["tiles_touched_all"]),
-                                       _p(st["keys"]), _p(st["stats"]), _stream()))
+    head = (arr, V, _p(st.cams_dev))
+    tail = (G, _p(means), _p(cov), _cov_stride(cov), _p(opac), _p(colors), channels, int(bool(sh_planar)), _p(st.rec), _p(st.radii), _p(st.rect),
+            _p(st.tiles_touched_all), _p(st.keys), _p(st.stats_dev), _stream())
+    if pose.kind == "host":
+        check(lib.siu3r_raster_project(*head, *tail))
     else:
-        vm, Ks = st["pose_dev"] = _pose_dev(pose_dev, V, dev)  # (kept with the state: the launches below read them asynchronously)
-        check(lib.siu3r_raster_project_dp(arr, V, _p(st["cams_dev"]), _p(vm), _p(Ks), G, _p(means), _p(cov), _cov_stride(cov), _p(opac), _p(colors),
-                                          channels, int(bool(sh_planar)), _p(st["rec"]), _p(st["radii"]), _p(st["rect"]),
-                                          _p(st["tiles_touched_all"]), _p(st["keys"]), _p(st["stats"]), _stream()))
+        st.pose_dev = (pose.a, pose.b)  # (kept with the state: the launches read them asynchronously)
+        if pose.kind == "c2w":
+            check(lib.siu3r_raster_project_c2w(*head, _p(pose.a), _p(pose.b), pose.t_scale, *tail))
+        else:
+            check(lib.siu3r_raster_project_dp(*head, _p(pose.a), _p(pose.b), *tail))
     rs_hist, rs_tot = i32(V, 256, geo["nchunks_sort"]), i32(V, 256)
-    check(lib.siu3r_raster_sort(V, G, _p(st["keys"]), _p(st["keys_b"]), _p(st["sorted_ids"]), _p(st["ids_b"]), _p(rs_hist), _p(rs_tot), _p(st["stats"]), _stream()))
+    check(lib.siu3r_raster_sort(V, G, _p(st.keys), _p(st.keys_b), _p(st.sorted_ids), _p(st.ids_b), _p(rs_hist), _p(rs_tot), _p(st.stats_dev), _stream()))
     bin_hist, bin_tot = i32(V, geo["NB"], geo["nchunks_bin"]), i32(V, geo["NB"])
-    st["bin_start"] = i32(V, geo["NB"] + 1)
-    st["entries"] = torch.empty((V, cap_e, 2), dtype=torch.int32, device=dev)
-    st["cap_e"] = cap_e
-    check(lib.siu3r_raster_bin(arr, V, G, _p(st["keys"]), _p(st["sorted_ids"]), _p(st["rect"]), _p(bin_hist), _p(bin_tot), _p(st["bin_start"]),
-                               _p(st["entries"]), cap_e, _p(st["stats"]), _stream()))
+    st.bin_start = i32(V, geo["NB"] + 1)
+    st.entries = torch.empty((V, cap_e, 2), dtype=torch.int32, device=dev)
+    check(lib.siu3r_raster_bin(arr, V, G, _p(st.keys), _p(st.sorted_ids), _p(st.rect), _p(bin_hist), _p(bin_tot), _p(st.bin_start), _p(st.entries), cap_e,
+                               _p(st.stats_dev), _stream()))
     return st
 
 
@@ -252,20 +271,21 @@ def _project_sort_bin(cams: Sequence[RasterCam], means, cov, opac, colors, chann
 # scene size -- so that the caller knows WHICH result to discard and repeat; the exception may surface at the start of a LATER deferred
 # call (which has not run yet) or at check_pending().  Callers in this repository: bench.py's render legs (check_pending() after the
 # timed calls); evaluate.py renders with the synchronous check (check_overflow=True: transparent repeat).
+_Pending = collections.namedtuple("_Pending", "event host cap_e key call_id")  # key = (G, V, W, H) of the call
 _PENDING: "collections.deque" = collections.deque()
 _PINNED_FREE: list = []
 _CALL_SEQ = [0]
 
 
-def _defer_check(st: "_State"):
-    stats = dict.__getitem__(st, "stats")
+def _defer_check(st: RasterState):
+    stats = st.stats_dev
     i = next((i for i, h in enumerate(_PINNED_FREE) if h.shape == stats.shape), None)
     host = _PINNED_FREE.pop(i) if i is not None else torch.empty(stats.shape, dtype=stats.dtype, pin_memory=True)
     host.copy_(stats, non_blocking=True)
     ev = torch.cuda.Event()
     ev.record()
     _CALL_SEQ[0] += 1
-    _PENDING.append((ev, host, dict.__getitem__(st, "cap_e"), (dict.__getitem__(st, "G"), dict.__getitem__(st, "V"), dict.__getitem__(st, "W"), dict.__getitem__(st, "H")), _CALL_SEQ[0]))
+    _PENDING.append(_Pending(ev, host, st.cap_e, (st.G, st.V, st.W, st.H), _CALL_SEQ[0]))
     return _CALL_SEQ[0]
 
 
@@ -274,20 +294,21 @@ def check_pending(block: bool = True):
     arrived).  Raises RasterOverflow for the first call that overflowed its entry buffers (its views were rendered as NaN)."""
     bad = None
     while _PENDING:
-        ev, host, cap_e, key, seq = _PENDING[0]
-        if not block and not ev.query():
+        p = _PENDING[0]
+        if not block and not p.event.query():
             break
-        ev.synchronize()
+        p.event.synchronize()
         _PENDING.popleft()
-        e_max = int(host[:, 2].max())
+        e_max = int(p.host[:, 2].max())
         if len(_PINNED_FREE) < 8:
-            _PINNED_FREE.append(host)
-        if e_max > cap_e:
-            _remember("entries", *key, e_max)
-            bad = bad or (e_max, cap_e, key, seq)
+            _PINNED_FREE.append(p.host)
+        if e_max > p.cap_e:
+            _remember("entries", *p.key, e_max)
+            bad = bad or (e_max, p)
     if bad:
-        raise RasterOverflow(f"deferred rasterizer call #{bad[3]} (G, V, W, H = {bad[2]}) overflowed its coarse-bin entries: E = {bad[0]} > entry_capacity "
-                             f"{bad[1]}; its views were rendered as NaN.  The needed capacity is remembered: repeat that call", call_id=bad[3])
+        e_max, p = bad
+        raise RasterOverflow(f"deferred rasterizer call #{p.call_id} (G, V, W, H = {p.key}) overflowed its coarse-bin entries: E = {e_max} > entry_capacity "
+                             f"{p.cap_e}; its views were rendered as NaN.  The needed capacity is remembered: repeat that call", call_id=p.call_id)
 
 
 def _with_retry(run, entry_capacity, check_overflow):
@@ -305,10 +326,69 @@ def _with_retry(run, entry_capacity, check_overflow):
         return out
     st = out["state"]
     e_max = max(st.totals(2))
-    if e_max > st["cap_e"]:
-        _remember("entries", st["G"], st["V"], st["W"], st["H"], e_max)
+    if e_max > st.cap_e:
+        _remember("entries", st.G, st.V, st.W, st.H, e_max)
         out = run(e_max)
         out["state"].verify()
+    return out
+
+
+def _render(cams, means, cov6, opacities, chan, channels, pose, entry_capacity, check_overflow, composite, sh_planar=False):
+    """The one render path (the entry points have checked the device).  chan: the call's colour block -- `channels` > 0: shs / rgb, which the
+    projection reads into the records; 0: feats, which only the composite reads.  composite(st, chan): allocate outputs, launch, return the dict."""
+    means, cov6, opacities, chan = (t.contiguous().float() for t in (means, cov6, opacities, chan))
+
+    def run(cap):
+        st = _project_sort_bin(cams, means, cov6, opacities, chan if channels else None, channels, cap, check_overflow, sh_planar, pose)
+        return composite(st, chan)
+
+    return _with_retry(run, entry_capacity, check_overflow)
+
+
+def _empty(st: RasterState, *shape, dtype=torch.float32):
+    return torch.empty(shape, dtype=dtype, device=st.rec.device)
+
+
+def _wants_grad(*ts) -> bool:
+    return torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in ts)
+
+
+def _no_deferred(check_overflow):
+    if check_overflow == "deferred":
+        raise ValueError('check_overflow="deferred" cannot be combined with gradients: the backward reuses the binning of the forward, which '
+                         "must be known complete (pass check_overflow=True)")
+
+
+def _forward(ctx, render, diff, keep, maps, aux):
+    """forward of the three autograd functions: render(the first four of the differentiable arguments `diff`, detached; synchronous overflow
+    check).  ctx keeps the state and what _grads_out needs of `diff`; saved: `keep` (inputs the backward reads again) and private copies of the
+    outputs `maps` (callers may modify the returned ones in place: image.clamp_(0, 1)); the outputs `aux` carry no gradient.  -> maps, aux, state"""
+    o = render(*(t.detach() for t in diff[:4]))
+    ctx.st = o["state"]
+    ctx.shapes = [(t.shape, t.dtype, t.device) if isinstance(t, torch.Tensor) else None for t in diff]
+    ctx.save_for_backward(*keep, *(o[k].clone() for k in maps))
+    ctx.mark_non_differentiable(*(o[k] for k in aux if o[k] is not None))
+    return (*(o[k] for k in maps + aux), ctx.st)
+
+
+def _backward_start(ctx, inputs, upstream):
+    """what the three backwards start from: the state; the saved `inputs` as the kernels read them (fp32, contiguous); the upstream gradients
+    of the (output, gradient) pairs likewise, zeros where autograd hands over None; the empty screen-space gradient buffer [V,G,GR_N]"""
+    st = ctx.st
+    return (st, [t.detach().contiguous().float() for t in inputs],
+            [torch.zeros_like(ref) if g is None else g.detach().float().contiguous() for ref, g in upstream], _empty(st, st.V, st.G, GR_N))
+
+
+def _grads_out(ctx, first, grads):
+    """the gradients of the differentiable inputs (index first.. of forward's arguments) in their shapes / dtypes / devices (a pose handed
+    over on the host gets its gradient there), None where not needed"""
+    out = []
+    for i, g in enumerate(grads):
+        if g is None or not ctx.needs_input_grad[first + i]:
+            out.append(None)
+            continue
+        shape, dtype, device = ctx.shapes[i]
+        out.append(g.reshape(shape).to(device=device, dtype=dtype))
     return out
 
 
@@ -326,21 +406,20 @@ def rasterize_views_k2(cams: Sequence[RasterCam], means, cov6, shs, opacities, w
     density_stats: a density.DensityStats of G Gaussians; the backward of a differentiable call accumulates the per-view NDC-space mean
     gradient norms (scaled by V: DensityStats.accumulate), the visibility counts and the largest radii into it.  The forward does not
     look at it, and None (the default) leaves the backward exactly as it is without the keyword."""
-    diff = (means, cov6, shs, opacities, pose_delta, means2d)
-    if torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in diff):
-        if check_overflow == "deferred":
-            raise ValueError('check_overflow="deferred" cannot be combined with gradients: the backward reuses the binning of the forward, which '
-                             "must be known complete (pass check_overflow=True)")
+    wants_grad = _wants_grad(means, cov6, shs, opacities, pose_delta, means2d)
+    if wants_grad:
+        _no_deferred(check_overflow)
         if pose_delta is not None and tuple(pose_delta.shape) != (len(cams), 6):
             raise ValueError(f"pose_delta must be [V, 6] = (rho, theta) per view, got {tuple(pose_delta.shape)}")
-        kw = dict(want_n_touched=want_n_touched, entry_capacity=entry_capacity, sh_planar=sh_planar, pose_c2w=pose_c2w)
-        if density_stats is not None:
-            if density_stats.G != means.shape[0]:
-                raise ValueError(f"density_stats holds {density_stats.G} Gaussians, the render has {means.shape[0]}")
-            kw["density_stats"] = density_stats
-        image, depth, opacity, radii, n_touched, st = _RasterizeK2.apply(list(cams), kw, means, cov6, shs, opacities, pose_delta, means2d)
-        return dict(image=image, radii=radii, depth=depth, opacity=opacity, n_touched=n_touched, state=st)
-    return _rasterize_views_k2(cams, means, cov6, shs, opacities, want_n_touched, entry_capacity, check_overflow, sh_planar, pose_c2w)
+        if density_stats is not None and density_stats.G != means.shape[0]:
+            raise ValueError(f"density_stats holds {density_stats.G} Gaussians, the render has {means.shape[0]}")
+    _gpu(means, cov6, shs, opacities)
+    pose = _pose(len(cams), means.device, pose_c2w=pose_c2w)
+    if not wants_grad:
+        return _rasterize_views_k2(cams, means, cov6, shs, opacities, want_n_touched, entry_capacity, check_overflow, sh_planar, pose)
+    render = lambda *gaussians: _rasterize_views_k2(cams, *gaussians, want_n_touched, entry_capacity, True, sh_planar, pose)
+    image, depth, opacity, radii, n_touched, st = _RasterizeK2.apply(render, sh_planar, density_stats, means, cov6, shs, opacities, pose_delta, means2d)
+    return dict(image=image, radii=radii, depth=depth, opacity=opacity, n_touched=n_touched, state=st)
 
 
 class _RasterizeK2(torch.autograd.Function):
@@ -348,33 +427,23 @@ class _RasterizeK2(torch.autograd.Function):
     per-(view, Gaussian) screen-space gradients -> projection backward -> Gaussians, pose (rho, theta) per view, pixel-space means."""
 
     @staticmethod
-    def forward(ctx, cams, kw, means, cov6, shs, opacities, pose_delta, means2d):
-        kw = dict(kw)
-        ctx.density_stats = kw.pop("density_stats", None)
-        o = _rasterize_views_k2(cams, means.detach(), cov6.detach(), shs.detach(), opacities.detach(), check_overflow=True, **kw)
-        st = o["state"]
-        ctx.st, ctx.sh_planar = st, kw["sh_planar"]
-        ctx.shapes = _shapes(means, cov6, shs, opacities, pose_delta, means2d)
-        # private copies of the totals the backward needs: callers may modify the returned maps in place (image.clamp_(0, 1))
-        ctx.save_for_backward(means, cov6, shs, opacities, o["image"].clone(), o["depth"].clone(), o["opacity"].clone())
-        nd = [o["radii"]] + ([o["n_touched"]] if o["n_touched"] is not None else [])
-        ctx.mark_non_differentiable(*nd)
-        return o["image"], o["depth"], o["opacity"], o["radii"], o["n_touched"], st
+    def forward(ctx, render, sh_planar, density_stats, means, cov6, shs, opacities, pose_delta, means2d):
+        ctx.sh_planar, ctx.density_stats = sh_planar, density_stats
+        gaussians = (means, cov6, shs, opacities)
+        return _forward(ctx, render, (*gaussians, pose_delta, means2d), gaussians, maps=("image", "depth", "opacity"), aux=("radii", "n_touched"))
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g_image, g_depth, g_opacity, _g_radii, _g_nt, _g_st):
-        means, cov6, shs, opacities, image, depth, opacity = ctx.saved_tensors
-        st = ctx.st
+        *inputs, image, depth, opacity = ctx.saved_tensors
+        st, (means_c, cov_c, shs_c, op_c), (g_image, g_depth, g_opacity), grad = _backward_start(
+            ctx, inputs, ((image, g_image), (depth, g_depth), (opacity, g_opacity)))
         lib = _lib.lib()
-        V, G, dev = st["V"], st["G"], image.device
-        g_image, g_depth, g_opacity = _upstream(image, g_image), _upstream(depth, g_depth), _upstream(opacity, g_opacity)
-        means_c, cov_c, shs_c, op_c = (t.detach().contiguous().float() for t in (means, cov6, shs, opacities))
+        V, G, dev = st.V, st.G, image.device
         ncoef = shs_c.shape[2] if ctx.sh_planar else shs_c.shape[1]
-        grad = torch.empty((V, G, GR_N), dtype=torch.float32, device=dev)
-        check(lib.siu3r_raster_composite_rgb_bwd(st["cams"], V, _p(st["cams_dev"]), G, _p(st["bin_start"]), _p(st["entries"]), st["cap_e"], _p(st["rec"]),
+        check(lib.siu3r_raster_composite_rgb_bwd(st.cams, V, _p(st.cams_dev), G, _p(st.bin_start), _p(st.entries), st.cap_e, _p(st.rec),
                                                  _p(image), _p(depth), _p(opacity), _p(g_image), _p(g_depth), _p(g_opacity), _p(grad), _stream()))
-        need_pose, need_m2d = ctx.needs_input_grad[6], ctx.needs_input_grad[7]
+        need_pose, need_m2d = ctx.needs_input_grad[7], ctx.needs_input_grad[8]
         stats = ctx.density_stats
         g_means, g_cov, g_op, g_sh = torch.empty_like(means_c), torch.empty_like(cov_c), torch.empty_like(op_c), torch.empty_like(shs_c)
         g_m2d = torch.zeros((V, G, 2), dtype=torch.float32, device=dev) if need_m2d else None  # (culled Gaussians: not written)
@@ -382,11 +451,11 @@ class _RasterizeK2(torch.autograd.Function):
             g_m2d = torch.empty((V, G, 2), dtype=torch.float32, device=dev)  # (the statistics go by the radii, never by an unwritten row)
         rows = int(lib.siu3r_raster_pose_partial_rows(G))
         part = torch.empty((max(rows, 1), V, 6), dtype=torch.float32, device=dev) if need_pose else None
-        check(lib.siu3r_raster_project_bwd(st["cams"], V, _p(st["cams_dev"]), G, _p(means_c), _p(cov_c), _cov_stride(cov_c), _p(op_c), _p(shs_c), ncoef,
-                                           int(bool(ctx.sh_planar)), _p(st["rect"]), _p(grad), _p(g_means), _p(g_cov), _p(g_op), _p(g_sh), _p(g_m2d),
+        check(lib.siu3r_raster_project_bwd(st.cams, V, _p(st.cams_dev), G, _p(means_c), _p(cov_c), _cov_stride(cov_c), _p(op_c), _p(shs_c), ncoef,
+                                           int(bool(ctx.sh_planar)), _p(st.rect), _p(grad), _p(g_means), _p(g_cov), _p(g_op), _p(g_sh), _p(g_m2d),
                                            _p(part), _stream()))
         if stats is not None:
-            stats.accumulate(g_m2d, st["radii"], 0.5 * V * st["W"], 0.5 * V * st["H"])
+            stats.accumulate(g_m2d, st.radii, 0.5 * V * st.W, 0.5 * V * st.H)
         g_pose = None
         if need_pose:
             g_pose = torch.empty((V, 6), dtype=torch.float32, device=dev)
@@ -398,28 +467,19 @@ class _RasterizeK2(torch.autograd.Function):
             shape, dtype, _ = ctx.shapes[5]
             g_mean2d = torch.zeros(shape, dtype=dtype, device=dev)
             g_mean2d[:, :2] = g_m2d.sum(0).to(dtype)
-        return (None, None, *_grads_out(ctx, 2, (g_means, g_cov, g_sh, g_op, g_pose)), g_mean2d)
+        return (None, None, None, *_grads_out(ctx, 3, (g_means, g_cov, g_sh, g_op, g_pose)), g_mean2d)
 
 
-def _rasterize_views_k2(cams: Sequence[RasterCam], means, cov6, shs, opacities, want_n_touched=True, entry_capacity=None,
-                       check_overflow=True, sh_planar=False, pose_c2w=None) -> Dict[str, torch.Tensor]:
-    _gpu(means, cov6, shs, opacities)
-    means, cov6, shs, opacities = (t.contiguous().float() for t in (means, cov6, shs, opacities))
-    V, G, dev = len(cams), means.shape[0], means.device
-    H, W = cams[0].height, cams[0].width
-    ncoef = shs.shape[2] if sh_planar else shs.shape[1]
+def _rasterize_views_k2(cams, means, cov6, shs, opacities, want_n_touched, entry_capacity, check_overflow, sh_planar, pose) -> Dict[str, torch.Tensor]:
+    def composite(st, _shs):
+        V, H, W = st.V, st.H, st.W
+        image, depth, alpha = _empty(st, V, 3, H, W), _empty(st, V, H, W), _empty(st, V, H, W)
+        n_touched = _empty(st, V, st.G, dtype=torch.int32) if want_n_touched else None
+        check(_lib.lib().siu3r_raster_composite_rgb(st.cams, st.V, _p(st.cams_dev), st.G, _p(st.bin_start), _p(st.entries), st.cap_e, _p(st.rec),
+                                                    _p(image), _p(depth), _p(alpha), _p(n_touched), _stream()))
+        return dict(image=image, radii=st.radii, depth=depth, opacity=alpha, n_touched=n_touched, state=st)
 
-    def run(cap):
-        st = _project_sort_bin(cams, means, cov6, opacities, shs, ncoef, cap, check_overflow, sh_planar, pose_c2w=pose_c2w)
-        image = torch.empty((V, 3, H, W), dtype=torch.float32, device=dev)
-        depth = torch.empty((V, H, W), dtype=torch.float32, device=dev)
-        alpha = torch.empty((V, H, W), dtype=torch.float32, device=dev)
-        n_touched = torch.empty((V, G), dtype=torch.int32, device=dev) if want_n_touched else None
-        check(_lib.lib().siu3r_raster_composite_rgb(st["cams"], V, _p(st["cams_dev"]), G, _p(st["bin_start"]), _p(st["entries"]), st["cap_e"],
-                                                    _p(st["rec"]), _p(image), _p(depth), _p(alpha), _p(n_touched), _stream()))
-        return dict(image=image, radii=st["radii"], depth=depth, opacity=alpha, n_touched=n_touched, state=st)
-
-    return _with_retry(run, entry_capacity, check_overflow)
+    return _render(cams, means, cov6, opacities, shs, shs.shape[2] if sh_planar else shs.shape[1], pose, entry_capacity, check_overflow, composite, sh_planar)
 
 
 def rasterize_k2(cam: RasterCam, means, cov6, shs, opacities, **kw) -> Dict[str, torch.Tensor]:
@@ -435,19 +495,21 @@ def tune(key: int, value: int) -> None:
     check(_lib.lib().siu3r_raster_tune(int(key), int(value)))
 
 
-def _upstream(ref, g):
-    """an upstream gradient as the kernels read it (fp32, contiguous); zeros like the output where autograd hands over None"""
-    return torch.zeros_like(ref) if g is None else g.detach().float().contiguous()
+def _k3_gate(check_overflow, means, cov6, opacities, chan, pose_dev):
+    """the grad gate of both K3 entry points -> (a gradient is wanted, the viewmats of pose_dev: the fifth differentiable argument)"""
+    vm = pose_dev[0] if pose_dev is not None else None
+    wants_grad = _wants_grad(means, cov6, opacities, chan, vm)
+    if wants_grad:
+        _no_deferred(check_overflow)
+    _gpu(means, cov6, opacities, chan)
+    return wants_grad, vm
 
 
-def _wants_grad(*ts) -> bool:
-    return torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad for t in ts)
-
-
-def _no_deferred(check_overflow):
-    if check_overflow == "deferred":
-        raise ValueError('check_overflow="deferred" cannot be combined with gradients: the backward reuses the binning of the forward, which '
-                         "must be known complete (pass check_overflow=True)")
+def _k3_call(function, render, wants_grad, *diff):
+    if not wants_grad:
+        return render(*diff[:4])
+    colors, alphas, radii, st = function.apply(render, *diff)
+    return dict(colors=colors, alphas=alphas, radii=radii, state=st)
 
 
 def rasterize_views_k3(cams: Sequence[RasterCam], means, cov6, opacities, feats, entry_capacity=None, pair_capacity=None,
@@ -459,42 +521,23 @@ def rasterize_views_k3(cams: Sequence[RasterCam], means, cov6, opacities, feats,
 
     Differentiable when grad mode is on and means / cov6 / opacities / feats / the viewmats of pose_dev require grad (_RasterizeK3; the
     outputs are the same bits as without grad).  The gradient is undefined for non-finite features.  Every other call runs the plain forward."""
-    vm = pose_dev[0] if pose_dev is not None else None
-    if _wants_grad(means, cov6, opacities, feats, vm):
-        _no_deferred(check_overflow)
-        kw = dict(entry_capacity=entry_capacity, pair_capacity=pair_capacity, matrix_form=matrix_form, pose_c2w=pose_c2w,
-                  Ks=None if pose_dev is None else pose_dev[1])
-        colors, alphas, radii, st = _RasterizeK3.apply(list(cams), kw, means, cov6, opacities, feats, vm)
-        return dict(colors=colors, alphas=alphas, radii=radii, state=st)
-    return _rasterize_views_k3(cams, means, cov6, opacities, feats, entry_capacity, pair_capacity, check_overflow, pose_dev, matrix_form, pose_c2w)
-
-
-def _shapes(*ts):
-    """what _grads_out needs of forward's differentiable arguments"""
-    return [(t.shape, t.dtype, t.device) if isinstance(t, torch.Tensor) else None for t in ts]
-
-
-def _grads_out(ctx, first, grads):
-    """the gradients of the differentiable inputs (index first.. of forward's arguments) in their shapes / dtypes / devices (a pose handed
-    over on the host gets its gradient there), None where not needed"""
-    out = []
-    for i, g in enumerate(grads):
-        if g is None or not ctx.needs_input_grad[first + i]:
-            out.append(None)
-            continue
-        shape, dtype, device = ctx.shapes[i]
-        out.append(g.reshape(shape).to(device=device, dtype=dtype))
-    return out
+    wants_grad, vm = _k3_gate(check_overflow, means, cov6, opacities, feats, pose_dev)
+    if check_overflow == "deferred":
+        raise ValueError('check_overflow="deferred" is only safe on the RGB composites (an overflowing view is NaN-poisoned there); the '
+                         "N-channel composite has no such marker: pass True (check now) or False (and call state.verify())")
+    pose, check = _pose(len(cams), means.device, pose_dev, pose_c2w), wants_grad or check_overflow
+    render = lambda m, c, o, f: _rasterize_views_k3(cams, m, c, o, f, entry_capacity, pair_capacity, check, pose, matrix_form)
+    return _k3_call(_RasterizeK3, render, wants_grad, means, cov6, opacities, feats, vm)
 
 
 def _project_bwd_k3(st, means, cov6, grad, need_pose, g_colors=None):
     """the mode-1 projection backward of a finished composite backward (grad [V,G,GR_N]) -> g_means, g_cov, g_opacities, g_viewmats [V,4,4]"""
     lib = _lib.lib()
-    V, G, dev = st["V"], st["G"], means.device
+    V, G, dev = st.V, st.G, means.device
     g_means, g_cov, g_op = torch.empty_like(means), torch.empty_like(cov6), torch.empty((G,), dtype=torch.float32, device=dev)
     rows = int(lib.siu3r_raster_pose_partial_rows(G))
     part = torch.zeros((max(rows, 1), V, 12), dtype=torch.float32, device=dev) if need_pose else None
-    check(lib.siu3r_raster_project_bwd_k3(st["cams"], V, _p(st["cams_dev"]), G, _p(means), _p(cov6), _cov_stride(cov6), _p(st["rect"]), _p(grad),
+    check(lib.siu3r_raster_project_bwd_k3(st.cams, V, _p(st.cams_dev), G, _p(means), _p(cov6), _cov_stride(cov6), _p(st.rect), _p(grad),
                                           _p(g_means), _p(g_cov), _p(g_op), _p(g_colors), _p(part), _stream()))
     g_vm = None
     if need_pose:
@@ -503,83 +546,54 @@ def _project_bwd_k3(st, means, cov6, grad, need_pose, g_colors=None):
     return g_means, g_cov, g_op, g_vm
 
 
-def _k3_forward(ctx, render, save_chan, cams, kw, means, cov6, opacities, chan, viewmats):
-    """forward of both K3 autograd functions: chan = feats [G,C] (which the N-channel backward reads again: save_chan) or rgb [G,3]"""
-    kw = dict(kw)
-    Ks = kw.pop("Ks")
-    pose_dev = None if viewmats is None else (viewmats, Ks)
-    o = render(cams, means.detach(), cov6.detach(), opacities.detach(), chan.detach(), check_overflow=True, pose_dev=pose_dev, **kw)
-    ctx.st = o["state"]
-    ctx.shapes = _shapes(means, cov6, opacities, chan, viewmats)
-    # private copies of the totals the backward needs: callers may modify the returned maps in place
-    ctx.save_for_backward(means, cov6, *((chan,) if save_chan else ()), o["colors"].clone(), o["alphas"].clone())
-    ctx.mark_non_differentiable(o["radii"])
-    return o["colors"], o["alphas"], o["radii"], o["state"]
-
-
 class _RasterizeK3(torch.autograd.Function):
     """The K3 N-channel forward (unchanged kernels, synchronous overflow check) and its HIP backward (csrc/raster_bwd_k3.hip): composite
     backward over the per-quadrant lists (the forward's workspace, or built here) -> per-(view, Gaussian) screen-space gradients and the
     feature gradient -> projection backward -> Gaussians and world->camera matrices."""
 
     @staticmethod
-    def forward(ctx, cams, kw, means, cov6, opacities, feats, viewmats):
-        return _k3_forward(ctx, _rasterize_views_k3, True, cams, kw, means, cov6, opacities, feats, viewmats)
+    def forward(ctx, render, means, cov6, opacities, feats, viewmats):
+        return _forward(ctx, render, (means, cov6, opacities, feats, viewmats), (means, cov6, feats), maps=("colors", "alphas"), aux=("radii",))  # (feats: read again)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g_colors, g_alphas, _g_radii, _g_st):
-        means, cov6, feats, colors, alphas = ctx.saved_tensors
-        st = ctx.st
+        *inputs, colors, alphas = ctx.saved_tensors
+        st, (means_c, cov_c, feats_c), (g_colors, g_alphas), grad = _backward_start(ctx, inputs, ((colors, g_colors), (alphas, g_alphas)))
         lib = _lib.lib()
-        V, G, dev = st["V"], st["G"], colors.device
-        g_colors, g_alphas = _upstream(colors, g_colors), _upstream(alphas, g_alphas)
-        means_c, cov_c, feats_c = (t.detach().contiguous().float() for t in (means, cov6, feats))
-        Cc = feats_c.shape[1]
-        tstart, ids_all, cap_d = st["tile_start_all"], st["ids_all"], st["cap_d"]
+        V, G = st.V, st.G
+        tstart, ids_all, cap_d = st.tile_start_all, st.ids_all, st.cap_d
         # the per-quadrant lists: the forward's when its matrix-core form built them, else built now (whichever forward kernel ran -- the
         # 32-channel one below 32 channels, after tune(0, 1) or for scenes past 32-bit offsets -- these lists give the same walk)
-        ws = st.get("feat_ws")
-        if not st.get("feat_ws_lists"):
+        ws = st.feat_ws
+        if not st.feat_ws_lists:
             if ws is None:
-                ws = torch.empty((int(lib.siu3r_raster_composite_feat_ws_bytes(st["W"], st["H"], V, cap_d)) // 4,), dtype=torch.int32, device=dev)
-            check(lib.siu3r_raster_quad_lists(st["cams"], V, _p(st["cams_dev"]), G, _p(tstart), _p(ids_all), cap_d, _p(st["rec"]), _p(ws),
-                                              ws.numel() * 4, _stream()))
-        grad = torch.empty((V, G, GR_N), dtype=torch.float32, device=dev)
+                ws = torch.empty((int(lib.siu3r_raster_composite_feat_ws_bytes(st.W, st.H, V, cap_d)) // 4,), dtype=torch.int32, device=colors.device)
+            check(lib.siu3r_raster_quad_lists(st.cams, V, _p(st.cams_dev), G, _p(tstart), _p(ids_all), cap_d, _p(st.rec), _p(ws), ws.numel() * 4, _stream()))
         g_feats = torch.empty_like(feats_c)
-        check(lib.siu3r_raster_composite_feat_bwd(st["cams"], V, _p(st["cams_dev"]), G, _p(tstart), _p(ws), cap_d, _p(st["rec"]), _p(feats_c), Cc,
+        check(lib.siu3r_raster_composite_feat_bwd(st.cams, V, _p(st.cams_dev), G, _p(tstart), _p(ws), cap_d, _p(st.rec), _p(feats_c), feats_c.shape[1],
                                                   _p(colors), _p(alphas), _p(g_colors), _p(g_alphas), _p(grad), _p(g_feats), _stream()))
-        g_means, g_cov, g_op, g_vm = _project_bwd_k3(st, means_c, cov_c, grad, ctx.needs_input_grad[6])
-        return (None, None, *_grads_out(ctx, 2, (g_means, g_cov, g_op, g_feats, g_vm)))
+        g_means, g_cov, g_op, g_vm = _project_bwd_k3(st, means_c, cov_c, grad, ctx.needs_input_grad[5])
+        return (None, *_grads_out(ctx, 1, (g_means, g_cov, g_op, g_feats, g_vm)))
 
 
-def _rasterize_views_k3(cams: Sequence[RasterCam], means, cov6, opacities, feats, entry_capacity=None, pair_capacity=None,
-                        check_overflow=True, pose_dev=None, matrix_form=True, pose_c2w=None) -> Dict[str, torch.Tensor]:
-    _gpu(means, cov6, opacities, feats)
-    if check_overflow == "deferred":
-        raise ValueError('check_overflow="deferred" is only safe on the RGB composites (an overflowing view is NaN-poisoned there); the '
-                         "N-channel composite has no such marker: pass True (check now) or False (and call state.verify())")
-    means, cov6, opacities, feats = (t.contiguous().float() for t in (means, cov6, opacities, feats))
-    V, G, dev = len(cams), means.shape[0], means.device
-    H, W, Cc = cams[0].height, cams[0].width, feats.shape[1]
-
-    def run(cap):
-        st = _project_sort_bin(cams, means, cov6, opacities, None, 0, cap, check_overflow, pose_dev=pose_dev, pose_c2w=pose_c2w)
-        st["cap_d_hint"] = int(pair_capacity) if pair_capacity else default_pair_capacity(G)
-        out = torch.empty((V, H, W, Cc), dtype=torch.float32, device=dev)
-        alpha = torch.empty((V, H, W), dtype=torch.float32, device=dev)
+def _rasterize_views_k3(cams, means, cov6, opacities, feats, entry_capacity, pair_capacity, check_overflow, pose, matrix_form) -> Dict[str, torch.Tensor]:
+    def composite(st, feats):
+        V, G, W, H, Cc = st.V, st.G, st.W, st.H, feats.shape[1]
+        st.cap_d_hint = int(pair_capacity) if pair_capacity else default_pair_capacity(G)
+        out, alpha = _empty(st, V, H, W, Cc), _empty(st, V, H, W)
         lib = _lib.lib()
-        tstart, ids_all, cap_d = st["tile_start_all"], st["ids_all"], st["cap_d"]
+        tstart, ids_all, cap_d = st.tile_start_all, st.ids_all, st.cap_d
         # workspace of the per-quadrant lists (C >= 32: every wave of the composite walks its own 8 x 8 quadrant's list)
-        ws = torch.empty((int(lib.siu3r_raster_composite_feat_ws_bytes(W, H, V, cap_d)) // 4,), dtype=torch.int32, device=dev) if (Cc >= 32 and matrix_form) else None
-        st["feat_ws"] = ws
+        ws = _empty(st, int(lib.siu3r_raster_composite_feat_ws_bytes(W, H, V, cap_d)) // 4, dtype=torch.int32) if (Cc >= 32 and matrix_form) else None
+        st.feat_ws = ws
         # (whether the forward leaves the per-quadrant lists in ws: a backward reuses them instead of building them again)
-        st["feat_ws_lists"] = ws is not None and bool(lib.siu3r_raster_composite_feat_ws_lists(W, H, V, G, _p(feats), Cc, _p(ws), ws.numel() * 4, cap_d))
-        check(lib.siu3r_raster_composite_feat_ws(st["cams"], V, _p(st["cams_dev"]), G, _p(tstart), _p(ids_all), cap_d, _p(st["rec"]), _p(feats), Cc,
+        st.feat_ws_lists = ws is not None and bool(lib.siu3r_raster_composite_feat_ws_lists(W, H, V, G, _p(feats), Cc, _p(ws), ws.numel() * 4, cap_d))
+        check(lib.siu3r_raster_composite_feat_ws(st.cams, V, _p(st.cams_dev), G, _p(tstart), _p(ids_all), cap_d, _p(st.rec), _p(feats), Cc,
                                                  _p(out), _p(alpha), _p(ws), 0 if ws is None else ws.numel() * 4, _stream()))
-        return dict(colors=out, alphas=alpha, radii=st["radii"], state=st)
+        return dict(colors=out, alphas=alpha, radii=st.radii, state=st)
 
-    return _with_retry(run, entry_capacity, check_overflow)
+    return _render(cams, means, cov6, opacities, feats, 0, pose, entry_capacity, check_overflow, composite)
 
 
 def rasterize_views_k3_rgb(cams: Sequence[RasterCam], means, cov6, opacities, rgb, entry_capacity=None, check_overflow=True,
@@ -589,13 +603,11 @@ def rasterize_views_k3_rgb(cams: Sequence[RasterCam], means, cov6, opacities, rg
     path materialises the lists because every 32-channel chunk re-walks them).
 
     Differentiable when grad mode is on and means / cov6 / opacities / rgb / the viewmats of pose_dev require grad (_RasterizeK3RGB)."""
-    vm = pose_dev[0] if pose_dev is not None else None
-    if _wants_grad(means, cov6, opacities, rgb, vm):
-        _no_deferred(check_overflow)
-        kw = dict(entry_capacity=entry_capacity, Ks=None if pose_dev is None else pose_dev[1])
-        colors, alphas, radii, st = _RasterizeK3RGB.apply(list(cams), kw, means, cov6, opacities, rgb, vm)
-        return dict(colors=colors, alphas=alphas, radii=radii, state=st)
-    return _rasterize_views_k3_rgb(cams, means, cov6, opacities, rgb, entry_capacity, check_overflow, pose_dev)
+    wants_grad, vm = _k3_gate(check_overflow, means, cov6, opacities, rgb, pose_dev)
+    assert rgb.shape[1] == 3
+    pose, check = _pose(len(cams), means.device, pose_dev), wants_grad or check_overflow
+    render = lambda m, c, o, r: _rasterize_views_k3_rgb(cams, m, c, o, r, entry_capacity, check, pose)
+    return _k3_call(_RasterizeK3RGB, render, wants_grad, means, cov6, opacities, rgb, vm)
 
 
 class _RasterizeK3RGB(torch.autograd.Function):
@@ -603,43 +615,29 @@ class _RasterizeK3RGB(torch.autograd.Function):
     bins like the forward, then the mode-1 projection backward (csrc/raster_bwd_k3.hip) takes the record colours' gradient to rgb."""
 
     @staticmethod
-    def forward(ctx, cams, kw, means, cov6, opacities, rgb, viewmats):
-        return _k3_forward(ctx, _rasterize_views_k3_rgb, False, cams, kw, means, cov6, opacities, rgb, viewmats)
+    def forward(ctx, render, means, cov6, opacities, rgb, viewmats):
+        return _forward(ctx, render, (means, cov6, opacities, rgb, viewmats), (means, cov6), maps=("colors", "alphas"), aux=("radii",))
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, g_colors, g_alphas, _g_radii, _g_st):
-        means, cov6, colors, alphas = ctx.saved_tensors
-        st = ctx.st
-        lib = _lib.lib()
-        V, G, dev = st["V"], st["G"], colors.device
-        g_colors, g_alphas = _upstream(colors, g_colors), _upstream(alphas, g_alphas)
-        means_c, cov_c = means.detach().contiguous().float(), cov6.detach().contiguous().float()
-        grad = torch.empty((V, G, GR_N), dtype=torch.float32, device=dev)
-        check(lib.siu3r_raster_composite_rgb_bwd_k3(st["cams"], V, _p(st["cams_dev"]), G, _p(st["bin_start"]), _p(st["entries"]), st["cap_e"],
-                                                    _p(st["rec"]), _p(colors), _p(alphas), _p(g_colors), _p(g_alphas), _p(grad), _stream()))
-        g_rgb = torch.empty((G, 3), dtype=torch.float32, device=dev)
-        g_means, g_cov, g_op, g_vm = _project_bwd_k3(st, means_c, cov_c, grad, ctx.needs_input_grad[6], g_colors=g_rgb)
-        return (None, None, *_grads_out(ctx, 2, (g_means, g_cov, g_op, g_rgb, g_vm)))
+        *inputs, colors, alphas = ctx.saved_tensors
+        st, (means_c, cov_c), (g_colors, g_alphas), grad = _backward_start(ctx, inputs, ((colors, g_colors), (alphas, g_alphas)))
+        check(_lib.lib().siu3r_raster_composite_rgb_bwd_k3(st.cams, st.V, _p(st.cams_dev), st.G, _p(st.bin_start), _p(st.entries), st.cap_e, _p(st.rec),
+                                                           _p(colors), _p(alphas), _p(g_colors), _p(g_alphas), _p(grad), _stream()))
+        g_rgb = torch.empty((st.G, 3), dtype=torch.float32, device=colors.device)
+        g_means, g_cov, g_op, g_vm = _project_bwd_k3(st, means_c, cov_c, grad, ctx.needs_input_grad[5], g_colors=g_rgb)
+        return (None, *_grads_out(ctx, 1, (g_means, g_cov, g_op, g_rgb, g_vm)))
 
 
-def _rasterize_views_k3_rgb(cams: Sequence[RasterCam], means, cov6, opacities, rgb, entry_capacity=None, check_overflow=True,
-                            pose_dev=None) -> Dict[str, torch.Tensor]:
-    _gpu(means, cov6, opacities, rgb)
-    means, cov6, opacities, rgb = (t.contiguous().float() for t in (means, cov6, opacities, rgb))
-    assert rgb.shape[1] == 3
-    V, G, dev = len(cams), means.shape[0], means.device
-    H, W = cams[0].height, cams[0].width
+def _rasterize_views_k3_rgb(cams, means, cov6, opacities, rgb, entry_capacity, check_overflow, pose) -> Dict[str, torch.Tensor]:
+    def composite(st, _rgb):
+        out, alpha = _empty(st, st.V, st.H, st.W, 3), _empty(st, st.V, st.H, st.W)
+        check(_lib.lib().siu3r_raster_composite_rgb(st.cams, st.V, _p(st.cams_dev), st.G, _p(st.bin_start), _p(st.entries), st.cap_e, _p(st.rec),
+                                                    _p(out), None, _p(alpha), None, _stream()))
+        return dict(colors=out, alphas=alpha, radii=st.radii, state=st)
 
-    def run(cap):
-        st = _project_sort_bin(cams, means, cov6, opacities, rgb, 3, cap, check_overflow, pose_dev=pose_dev)
-        out = torch.empty((V, H, W, 3), dtype=torch.float32, device=dev)
-        alpha = torch.empty((V, H, W), dtype=torch.float32, device=dev)
-        check(_lib.lib().siu3r_raster_composite_rgb(st["cams"], V, _p(st["cams_dev"]), G, _p(st["bin_start"]), _p(st["entries"]), st["cap_e"],
-                                                    _p(st["rec"]), _p(out), None, _p(alpha), None, _stream()))
-        return dict(colors=out, alphas=alpha, radii=st["radii"], state=st)
-
-    return _with_retry(run, entry_capacity, check_overflow)
+    return _render(cams, means, cov6, opacities, rgb, 3, pose, entry_capacity, check_overflow, composite)
 
 
 def rasterize_k3(cam: RasterCam, means, cov6, opacities, feats, **kw) -> Dict[str, torch.Tensor]:
