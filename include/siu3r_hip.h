@@ -196,8 +196,17 @@ typedef struct {
   int32_t kv_x3;        /* bf16x3 (fp32 tensors, split3): k and v point at PRE-SPLIT planes -- per token and head the 64 dims as two 128-byte
                            segments [hi 32 | lo 32] bf16, as a projection GEMM writes them with c_x3 / c_x3_col0 -- same strides as the
                            fp32 tensors.  Served by the pipelined kernel only (siu3r_attention_kv_x3_ok); anything else is an error. */
+  int32_t out_x3;       /* bf16x3: `out` is written as PRE-SPLIT planes instead of fp32 values -- per query and 32 columns one 128-byte line
+                           [hi 32 | lo 32] bf16 (hi = the upper 16 bits, lo = bf16(value - hi)), the A operand a ping-pong GEMM reads with
+                           siu3r_gemm_params.a_x3 -- same size and strides as the fp32 output.  Every store of the pipelined kernel (query
+                           body, key-half merge, side-path query) has this form; served by that kernel only, `out` 128-byte aligned
+                           (siu3r_attention_out_x3_ok); anything else is refused before a launch.  (The field takes the struct's tail
+                           padding: a zero-initialised block of an older caller means fp32.) */
 } siu3r_attn_params;
 int siu3r_attention(const siu3r_attn_params* p, void* stream);
+/* 1 if siu3r_attention would accept these parameters with out_x3 = 1 (the pipelined kernel's conditions: head_dim 64, no mask / RoPE-on-load /
+ * key split, >= 64 keys, fp32 + split3; `out` 128-byte aligned), else 0 */
+int siu3r_attention_out_x3_ok(const siu3r_attn_params* p);
 /* 1 if siu3r_attention would accept these parameters with kv_x3 = 1 (head_dim 64, no mask / RoPE-on-load / key split, >= 64 keys,
  * fp32 + split3, segment-aligned K / V rows), else 0 */
 int siu3r_attention_kv_x3_ok(const siu3r_attn_params* p);
@@ -240,6 +249,17 @@ int siu3r_resize_bilinear(const void* x, int x_dtype, void* y, int y_dtype, cons
 int siu3r_resize_bilinear_strided(const void* x, int x_dtype, void* y, int y_dtype, const void* addend, int add_dtype,
                                   const float* ch_scale, const float* ch_shift, int N, int IH, int IW, int OH, int OW,
                                   int C, int align_corners, int64_t x_batch_stride, int64_t addend_batch_stride, void* stream);
+/* PLANES OUTPUT of the producers whose only reader is a bf16x3 GEMM (siu3r_resize_bilinear_planes, siu3r_dwconv3x3_gelu_planes,
+ * siu3r_msdeform_sample_planes; the attention kernel has siu3r_attn_params.out_x3): the fp32 result is not stored; in its place, with the
+ * size and strides of the fp32 tensor, go the pre-split planes a ping-pong GEMM reads as its A operand (siu3r_gemm_params.a_x3) -- per row
+ * and 32 columns one 128-byte line [hi 32 | lo 32] bf16, hi = the upper 16 bits of the value, lo = bf16(value - hi), the split of the
+ * GEMM's K loop and of its c_x3 epilogue (csrc/common.h split_trunc_bf16x2), so that the consumer multiplies the same bits.
+ * REFUSED before anything is launched (non-zero return, siu3r_last_error, nothing written): a row width that is not a multiple of 32
+ * (C % 32, heads * d % 32), a planes pointer that is not 128-byte aligned, and what the fp32 entry point refuses.  An empty input
+ * returns 0 as above.  A caller whose shape does not qualify keeps the fp32 entry point. */
+/* the plain resize (no addend, no scale / shift) of siu3r_resize_bilinear_strided, fp32 planes out */
+int siu3r_resize_bilinear_planes(const void* x, int x_dtype, void* y_planes, int N, int IH, int IW, int OH, int OW, int C, int align_corners,
+                                 int64_t x_batch_stride, void* stream);
 /* y = x*scale[c] + shift[c] (+ addend) ; eval-mode BatchNorm folded (vit_adapter.py:436-440) */
 int siu3r_affine_add(const void* x, int x_dtype, const void* addend, int add_dtype, void* y, int y_dtype,
                      const float* ch_scale, const float* ch_shift, int64_t rows, int C, void* stream);
@@ -274,12 +294,18 @@ int siu3r_proj_rows_x3(const float* x, const void* wfrag, const float* bias, flo
 /* depth-wise 3x3 + bias + GELU over the 3 token scales of the adapter ConvFFN (vit_adapter.py:16-59) */
 int siu3r_dwconv3x3_gelu(const void* x, void* y, int dtype, const float* w9c, const float* bias, int B, int H,
                          int W, int C, void* stream);
+/* the same with fp32 x and the result as pre-split planes (PLANES OUTPUT above: C % 32 == 0) */
+int siu3r_dwconv3x3_gelu_planes(const float* x, void* y_planes, const float* w9c, const float* bias, int B, int H, int W, int C, void* stream);
 /* multi-scale deformable attention sampling core (vit_adapter/blocks.py:217-267):
  * value [B,S,heads,d]; offs_aw fp32 [B,Q,heads*L*P*3] = per row [offsets (h,L,P,2) | logits (h,L,P)];
  * ref fp32 [Q,L,2]; shapes int32 [L,2] (h,w) host pointer; out [B,Q,heads*d]. */
 int siu3r_msdeform_sample(const void* value, int v_dtype, const float* offs_aw, const float* ref,
                           const int32_t* shapes_host, void* out, int out_dtype, int B, int S, int Q, int heads,
                           int d, int L, int P, void* stream);
+/* the same with the result as pre-split planes (PLANES OUTPUT above: heads * d % 32 == 0).  Only the kernels specialised for the level
+ * count write planes: L = 1, 3 or 4 with P = 4 and a 16-byte aligned offs_aw; anything else is refused. */
+int siu3r_msdeform_sample_planes(const void* value, int v_dtype, const float* offs_aw, const float* ref, const int32_t* shapes_host,
+                                 void* out_planes, int B, int S, int Q, int heads, int d, int L, int P, void* stream);
 /* GroupNorm(32) on NHWC (video_seg_decoder.py:2002-2050): two kernels, stats then apply
  * y = relu?(gn(x)) + addend? ; stats is a [N,groups,2] fp32 workspace */
 int siu3r_groupnorm(const void* x, int x_dtype, void* y, int y_dtype, const float* gamma, const float* beta,

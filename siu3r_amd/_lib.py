@@ -63,7 +63,7 @@ class AttnParams(C.Structure):
         ("rope_cos", C.c_void_p), ("rope_sin", C.c_void_p), ("rope_max_pos", C.c_int32),
         ("qpos", C.c_void_p), ("kpos", C.c_void_p), ("mask", C.c_void_p),
         ("split3", C.c_int32), ("mask_ld", C.c_int64),
-        ("ws", C.c_void_p), ("splits", C.c_int32), ("kv_bxor", C.c_int32), ("kv_x3", C.c_int32),
+        ("ws", C.c_void_p), ("splits", C.c_int32), ("kv_bxor", C.c_int32), ("kv_x3", C.c_int32), ("out_x3", C.c_int32),
     ]
 
 
@@ -113,12 +113,14 @@ SIGNATURES = {
     "siu3r_layernorm2": [_P, _P, _I, _P, _P, _P, _L, _I, _L, _L, _L, _F, _P],
     "siu3r_attention": [C.POINTER(AttnParams), _P],
     "siu3r_attention_kv_x3_ok": [C.POINTER(AttnParams)],
+    "siu3r_attention_out_x3_ok": [C.POINTER(AttnParams)],
     "siu3r_attention_plan": [C.POINTER(AttnParams), C.POINTER(AttnPlan)],
     "siu3r_add": [_P, _P, _P, _L, _L, _I, _P],
     "siu3r_pack_image_nhwc": [_P, _P, _I, _I, _I, _I, _I, _P],
     "siu3r_resize_bilinear": [_P, _I, _P, _I, _P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P],
     "siu3r_affine_add": [_P, _I, _P, _I, _P, _I, _P, _P, _L, _I, _P],
     "siu3r_resize_bilinear_strided": [_P, _I, _P, _I, _P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _I, _L, _L, _P],
+    "siu3r_resize_bilinear_planes": [_P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _L, _P],
     "siu3r_affine_add_strided": [_P, _I, _P, _I, _P, _I, _P, _P, _L, _I, _L, _L, _L, _P],
     "siu3r_maxpool3x3s2": [_P, _P, _I, _I, _I, _I, _I, _P],
     "siu3r_maxpool2x2s2": [_P, _P, _I, _I, _I, _I, _I, _P],
@@ -126,6 +128,8 @@ SIGNATURES = {
     "siu3r_stem7x7_x3": [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _P],
     "siu3r_proj_rows_x3": [_P, _P, _P, _P, _I, _I, _L, _I, _I, _I, _L, _P],
     "siu3r_dwconv3x3_gelu": [_P, _P, _I, _P, _P, _I, _I, _I, _I, _P],
+    "siu3r_dwconv3x3_gelu_planes": [_P, _P, _P, _P, _I, _I, _I, _I, _P],
+    "siu3r_msdeform_sample_planes": [_P, _I, _P, _P, C.POINTER(C.c_int32), _P, _I, _I, _I, _I, _I, _I, _I, _P],
     "siu3r_msdeform_sample": [_P, _I, _P, _P, C.POINTER(C.c_int32), _P, _I, _I, _I, _I, _I, _I, _I, _I, _P],
     "siu3r_groupnorm": [_P, _I, _P, _I, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _F, _P],
     "siu3r_pts3d_exp": [_P, _L, _P],

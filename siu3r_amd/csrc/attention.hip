@@ -893,6 +893,13 @@ static bool kv_x3_ok(const siu3r_attn_params& p) {
 
 extern "C" int siu3r_attention_kv_x3_ok(const siu3r_attn_params* pp) { return pp && kv_x3_ok(*pp) ? 1 : 0; }
 
+// the output as pre-split planes: the pipelined bf16x3 kernel's stores only; a row of H * 64 columns is whole segments behind an aligned base
+static bool out_x3_ok(const siu3r_attn_params& p) {
+  return !attn_no_fast() && p.dtype == SIU3R_F32 && p.split3 && ((uintptr_t)p.out % 128) == 0 && siu3r_attn_pipe_ok(p);
+}
+
+extern "C" int siu3r_attention_out_x3_ok(const siu3r_attn_params* pp) { return pp && out_x3_ok(*pp) ? 1 : 0; }
+
 // parameter validation shared by siu3r_attention and siu3r_attention_plan
 static int validate_attn(const siu3r_attn_params& p) {
   SIU3R_CHECK(p.q && p.k && p.v && p.out, "siu3r_attention: null pointer");
@@ -912,6 +919,8 @@ static int validate_attn(const siu3r_attn_params& p) {
               "siu3r_attention: q/k/v strides must keep 16-byte alignment");
   SIU3R_CHECK(!p.kv_x3 || kv_x3_ok(p), "siu3r_attention: kv_x3 (pre-split K / V planes) needs the pipelined bf16x3 kernel (head_dim 64, no mask / RoPE on load / "
               "key split, >= 64 keys) and segment-aligned K / V: query siu3r_attention_kv_x3_ok first");
+  SIU3R_CHECK(!p.out_x3 || out_x3_ok(p), "siu3r_attention: out_x3 (pre-split output planes) needs the pipelined bf16x3 kernel (head_dim 64, no mask / RoPE on load / "
+              "key split, >= 64 keys) and a 128-byte aligned output: query siu3r_attention_out_x3_ok first");
   return 0;
 }
 

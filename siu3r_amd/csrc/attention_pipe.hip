@@ -501,8 +501,19 @@ __global__ __launch_bounds__(NT) void attn_pipe_kernel(const siu3r_attn_params p
         o += w * xq[g * (D + 2) + lane];
       }
       unsigned char* op = (unsigned char*)p.out + (((int64_t)b * p.Nq + (p.Nq - 1)) * ((int64_t)p.H * D) + (int64_t)h * D + lane) * OESZ;
-      if constexpr (X3) *(float*)op = o / L;
-      else *(u16*)op = f32_to_bf16_bits(o / L);
+      if constexpr (X3) {
+        if (p.out_x3) {  // planes: lane = d holds one bf16 of the hi half and one of the lo half of segment d / 32 (64-byte runs per 32 lanes)
+          uint32_t hi, lo;
+          split_trunc_bf16x2(o / L, 0.f, hi, lo);
+          u16* seg = (u16*)(op - lane * 4 + (lane >> 5) * 128);
+          seg[lane & 31] = (u16)hi;
+          seg[32 + (lane & 31)] = (u16)lo;
+        } else {
+          *(float*)op = o / L;
+        }
+      } else {
+        *(u16*)op = f32_to_bf16_bits(o / L);
+      }
     }
     return;
   }
@@ -521,7 +532,18 @@ __global__ __launch_bounds__(NT) void attn_pipe_kernel(const siu3r_attn_params p
       for (int e = 0; e < 4; ++e) o[e] = (oacc[dt][4 * g + e] * w0 + xs[l31 * (D + 2) + dt * 32 + 8 * g + 4 * lh + e] * w1) * inv;
       const int d = dt * 32 + 8 * g + 4 * lh;
       if constexpr (X3) {
-        *(float4*)(op + d * 4) = make_float4(o[0], o[1], o[2], o[3]);
+        if (p.out_x3) {
+          // planes: lanes l and l ^ 32 hold the 8 columns 8 g .. 8 g + 7 of segment dt of the same query.  One v_permlane32_swap per word
+          // (first operand hi, second lo) leaves the lower lane with both hi halves and the upper lane with both lo halves, in column
+          // order: 16 bytes of the hi plane from the lower lane, 16 bytes of the lo plane from the upper one
+          uint32_t hi[2], lo[2];
+          split_trunc_bf16x2(o[0], o[1], hi[0], lo[0]);
+          split_trunc_bf16x2(o[2], o[3], hi[1], lo[1]);
+          const auto s0 = __builtin_amdgcn_permlane32_swap(hi[0], lo[0], false, false), s1 = __builtin_amdgcn_permlane32_swap(hi[1], lo[1], false, false);
+          *(uint4*)(op + dt * 128 + lh * 64 + g * 16) = make_uint4(s0[0], s1[0], s0[1], s1[1]);
+        } else {
+          *(float4*)(op + d * 4) = make_float4(o[0], o[1], o[2], o[3]);
+        }
       } else {
         uint2 w;
         w.x = pack_bf16x2(o[0], o[1]);

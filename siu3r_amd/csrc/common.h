@@ -136,22 +136,38 @@ __device__ inline void split_bf16x8(const float* f, uint4& hi, uint4& lo) {
 }
 
 // the split of the GEMM K loop and of the pre-split planes (siu3r_gemm_params.c_x3): hi = the UPPER 16 BITS, lo = bf16(f - hi)
-__device__ inline void split_trunc_bf16x8(const float* f, uint4& hi, uint4& lo) {
-  float r[8];
-  uint32_t h[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    const uint32_t u0 = __float_as_uint(f[2 * j]), u1 = __float_as_uint(f[2 * j + 1]);
+// (one pair: hi and lo words of two consecutive values, the first in the low half)
+__device__ inline void split_trunc_bf16x2(float f0, float f1, uint32_t& hi, uint32_t& lo) {
+  const uint32_t u0 = __float_as_uint(f0), u1 = __float_as_uint(f1);
 #if __HIP_DEVICE_COMPILE__
-    h[j] = __builtin_amdgcn_perm(u1, u0, 0x07060302u);
+  hi = __builtin_amdgcn_perm(u1, u0, 0x07060302u);
 #else
-    h[j] = (u1 & 0xffff0000u) | (u0 >> 16);
+  hi = (u1 & 0xffff0000u) | (u0 >> 16);
 #endif
-    r[2 * j] = f[2 * j] - __uint_as_float(u0 & 0xffff0000u);
-    r[2 * j + 1] = f[2 * j + 1] - __uint_as_float(u1 & 0xffff0000u);
-  }
+  lo = pack_bf16x2(f0 - __uint_as_float(u0 & 0xffff0000u), f1 - __uint_as_float(u1 & 0xffff0000u));
+}
+__device__ inline void split_trunc_bf16x8(const float* f, uint4& hi, uint4& lo) {
+  uint32_t h[4], l[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) split_trunc_bf16x2(f[2 * j], f[2 * j + 1], h[j], l[j]);
   hi = make_uint4(h[0], h[1], h[2], h[3]);
-  lo = pack_bf16x8(r);
+  lo = make_uint4(l[0], l[1], l[2], l[3]);
+}
+
+// Plane store of a producer kernel whose lane holds 4 consecutive fp32 values of a row (columns c .. c + 3, c % 4 == 0) while its
+// neighbour lane (lane ^ 1) holds the 4 columns next to them (c ^ 4): the two lanes trade halves (DPP quad_perm [1,0,3,2], as the GEMM
+// row pass does) so that the even lane stores the 16 bytes of the hi plane and the odd lane the 16 bytes of the lo plane of their 8
+// columns.  `row` points at the row's first byte (planes have the fp32 tensor's strides); BOTH lanes of a pair must be active.
+__device__ __forceinline__ void store_planes4_pair(unsigned char* row, int c, const float (&v)[4]) {
+  uint32_t hi[2], lo[2], got[2];
+  split_trunc_bf16x2(v[0], v[1], hi[0], lo[0]);
+  split_trunc_bf16x2(v[2], v[3], hi[1], lo[1]);
+  const bool odd = (c & 4) != 0;
+#pragma unroll
+  for (int e = 0; e < 2; ++e) got[e] = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)(odd ? hi[e] : lo[e]), 0xB1 /* quad_perm [1,0,3,2] */, 0xF, 0xF, true);
+  const uint4 w = odd ? make_uint4(got[0], got[1], lo[0], lo[1]) : make_uint4(hi[0], hi[1], got[0], got[1]);
+  // segment (c >> 5): 128 bytes = [hi 32 | lo 32]; the pair's 8 columns are 16 bytes of either plane
+  *(uint4*)(row + (c >> 5) * 128 + (odd ? 64 : 0) + ((c & 31) >> 3) * 16) = w;
 }
 
 __device__ inline bf16x8 as_bf16x8(uint4 u) {

@@ -182,7 +182,7 @@ __device__ __forceinline__ void src_index(int o, int in, int out, int align, int
 
 __global__ void resize_kernel(const void* x, int x_dtype, void* y, int y_dtype, const void* addend, int add_dtype,
                               const float* ch_scale, const float* ch_shift, int N, int IH, int IW, int OH, int OW,
-                              int C, int align, int64_t x_bs, int64_t add_bs) {
+                              int C, int align, int64_t x_bs, int64_t add_bs, int y_x3) {
   const int C4 = C >> 2;
   const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int64_t total = (int64_t)N * OH * OW * C4;
@@ -215,6 +215,10 @@ __global__ void resize_kernel(const void* x, int x_dtype, void* y, int y_dtype, 
   if (ch_scale) {
 #pragma unroll
     for (int j = 0; j < 4; ++j) o.v[j] = o.v[j] * ch_scale[c + j] + ch_shift[c + j];
+  }
+  if (y_x3) {  // pre-split planes instead of fp32 values (C % 32 == 0: lanes t, t ^ 1 hold 8 columns of one pixel and are both active)
+    store_planes4_pair((unsigned char*)y + (oidx - c) * 4, c, o.v);
+    return;
   }
   store4(y, y_dtype, oidx, o);
 }
@@ -326,8 +330,9 @@ __global__ __launch_bounds__(256) void lpips_layer_kernel(const float* __restric
 
 // ================================ depth-wise 3x3 + bias + GELU over 3 token scales =============
 // tokens [B, 21n, C]: [0,16n) is a (2H x 2W) map, [16n,20n) (H x W), [20n,21n) (H/2 x W/2)
+// y_x3: y is written as pre-split planes (fp32 x; C % 32 == 0, so lanes t and t ^ 1 hold 8 columns of one token and are both active)
 __global__ void dwconv_gelu_kernel(const void* x, void* y, int dtype, const float* w9c, const float* bias, int B,
-                                   int H, int W, int C) {
+                                   int H, int W, int C, int y_x3) {
   const int C4 = C >> 2;
   const int n = (H * W) / 4;
   const int ntok = 21 * n;
@@ -366,6 +371,10 @@ __global__ void dwconv_gelu_kernel(const void* x, void* y, int dtype, const floa
   }
 #pragma unroll
   for (int j = 0; j < 4; ++j) acc.v[j] = gelu_erf(acc.v[j]);
+  if (y_x3) {
+    store_planes4_pair((unsigned char*)y + (idx * 4 - c) * 4, c, acc.v);
+    return;
+  }
   store4(y, dtype, idx * 4, acc);
 }
 
@@ -379,7 +388,7 @@ struct MsdShapes {
 // samples that have it as an in-range corner) and the compiler issues a point's four 16-byte gathers together.  LT = 0: any L <= 4, any P.
 template <int LT, int PT>
 __global__ __launch_bounds__(256, 4) void msdeform_kernel(const void* value, int v_dtype, const float* offs_aw, const float* ref, MsdShapes sh,
-                                                       void* out, int out_dtype, int B, int S, int Q, int heads, int d, int L, int P, int qb) {
+                                                       void* out, int out_dtype, int B, int S, int Q, int heads, int d, int L, int P, int qb, int out_x3) {
   const int D4 = d >> 2;
   int dc, hd, q, b;
   if (qb > 0) {
@@ -470,6 +479,12 @@ __global__ __launch_bounds__(256, 4) void msdeform_kernel(const void* value, int
         for (int k = 0; k < 4; ++k)
 #pragma unroll
           for (int j = 0; j < 4; ++j) acc.v[j] += v[pt][k].v[j] * wk[pt][k];
+    }
+    if (out_x3) {
+      // pre-split planes (rows of heads * d columns, a multiple of 32): lanes t and t ^ 1 hold 8 columns of one row -- of one head when
+      // d % 8 == 0, else the host picked the flat thread order, where consecutive threads are consecutive columns -- and are both active
+      store_planes4_pair((unsigned char*)out + ((int64_t)b * Q + q) * heads * d * 4, hd * d + dc, acc.v);
+      return;
     }
     store4(out, out_dtype, (((int64_t)b * Q + q) * heads + hd) * d + dc, acc);
   } else {
@@ -844,8 +859,20 @@ extern "C" int siu3r_resize_bilinear_strided(const void* x, int x_dtype, void* y
   SIU3R_CHECK(al4(x, x_dtype) && al4(y, y_dtype) && al4(addend, add_dtype), "resize_bilinear: x, y, addend must be 16-byte (fp32) / 8-byte (bf16) aligned");
   SIU3R_CHECK(x_batch_stride >= (int64_t)IH * IW * C && x_batch_stride % 4 == 0 && (!addend || (addend_batch_stride >= (int64_t)OH * OW * C && addend_batch_stride % 4 == 0)),
               "resize_bilinear: batch strides must cover one map and keep 4-element alignment");
-  hipLaunchKernelGGL(resize_kernel, grid1d((int64_t)N * OH * OW * (C / 4)), dim3(256), 0, (hipStream_t)stream, x, x_dtype, y, y_dtype, addend, add_dtype, ch_scale, ch_shift, N, IH, IW, OH, OW, C, align_corners, x_batch_stride, addend_batch_stride);
+  hipLaunchKernelGGL(resize_kernel, grid1d((int64_t)N * OH * OW * (C / 4)), dim3(256), 0, (hipStream_t)stream, x, x_dtype, y, y_dtype, addend, add_dtype, ch_scale, ch_shift, N, IH, IW, OH, OW, C, align_corners, x_batch_stride, addend_batch_stride, 0);
   SIU3R_LAUNCH_CHECK("siu3r_resize_bilinear");
+  return 0;
+}
+
+extern "C" int siu3r_resize_bilinear_planes(const void* x, int x_dtype, void* y_planes, int N, int IH, int IW, int OH, int OW, int C, int align_corners,
+                                            int64_t x_batch_stride, void* stream) {
+  SIU3R_CHECK(C % 32 == 0, "resize_bilinear_planes: planes need whole 32-column segments (C=%d)", C);
+  if ((int64_t)N * OH * OW * C == 0) return 0;
+  SIU3R_CHECK(x && y_planes && IH > 0 && IW > 0, "resize_bilinear_planes: null pointer or empty source");
+  SIU3R_CHECK(al4(x, x_dtype) && ((uintptr_t)y_planes & 127) == 0, "resize_bilinear_planes: x must be 16-byte (fp32) / 8-byte (bf16) aligned, the planes 128-byte aligned");
+  SIU3R_CHECK(x_batch_stride >= (int64_t)IH * IW * C && x_batch_stride % 4 == 0, "resize_bilinear_planes: the batch stride must cover one map and keep 4-element alignment");
+  hipLaunchKernelGGL(resize_kernel, grid1d((int64_t)N * OH * OW * (C / 4)), dim3(256), 0, (hipStream_t)stream, x, x_dtype, y_planes, SIU3R_F32, nullptr, SIU3R_F32, nullptr, nullptr, N, IH, IW, OH, OW, C, align_corners, x_batch_stride, (int64_t)OH * OW * C, 1);
+  SIU3R_LAUNCH_CHECK("siu3r_resize_bilinear_planes");
   return 0;
 }
 
@@ -913,14 +940,25 @@ extern "C" int siu3r_dwconv3x3_gelu(const void* x, void* y, int dtype, const flo
   if ((int64_t)B * ntok * C == 0) return 0;
   SIU3R_CHECK(x && y && w9c && bias, "dwconv3x3_gelu: null pointer");
   SIU3R_CHECK(al4(x, dtype) && al4(y, dtype) && al16(w9c), "dwconv3x3_gelu: x, y must be 16-byte (fp32) / 8-byte (bf16) aligned, w9c 16");
-  hipLaunchKernelGGL(dwconv_gelu_kernel, grid1d((int64_t)B * ntok * (C / 4)), dim3(256), 0, (hipStream_t)stream, x, y, dtype, w9c, bias, B, H, W, C);
+  hipLaunchKernelGGL(dwconv_gelu_kernel, grid1d((int64_t)B * ntok * (C / 4)), dim3(256), 0, (hipStream_t)stream, x, y, dtype, w9c, bias, B, H, W, C, 0);
   SIU3R_LAUNCH_CHECK("siu3r_dwconv3x3_gelu");
   return 0;
 }
 
-extern "C" int siu3r_msdeform_sample(const void* value, int v_dtype, const float* offs_aw, const float* ref,
-                                     const int32_t* shapes_host, void* out, int out_dtype, int B, int S, int Q,
-                                     int heads, int d, int L, int P, void* stream) {
+extern "C" int siu3r_dwconv3x3_gelu_planes(const float* x, void* y_planes, const float* w9c, const float* bias, int B, int H, int W, int C, void* stream) {
+  SIU3R_CHECK(C % 32 == 0 && H % 2 == 0 && W % 2 == 0, "dwconv3x3_gelu_planes: planes need whole 32-column segments (C=%d) and even H, W", C);
+  const int64_t ntok = 21 * (int64_t)(H * W / 4);
+  if ((int64_t)B * ntok * C == 0) return 0;
+  SIU3R_CHECK(x && y_planes && w9c && bias, "dwconv3x3_gelu_planes: null pointer");
+  SIU3R_CHECK(al16(x) && al16(w9c) && ((uintptr_t)y_planes & 127) == 0, "dwconv3x3_gelu_planes: x, w9c must be 16-byte aligned, the planes 128-byte aligned");
+  hipLaunchKernelGGL(dwconv_gelu_kernel, grid1d((int64_t)B * ntok * (C / 4)), dim3(256), 0, (hipStream_t)stream, x, y_planes, SIU3R_F32, w9c, bias, B, H, W, C, 1);
+  SIU3R_LAUNCH_CHECK("siu3r_dwconv3x3_gelu_planes");
+  return 0;
+}
+
+// out_x3: `out` as pre-split planes (siu3r_msdeform_sample_planes)
+static int msdeform_sample(const void* value, int v_dtype, const float* offs_aw, const float* ref, const int32_t* shapes_host, void* out, int out_dtype,
+                           int B, int S, int Q, int heads, int d, int L, int P, int out_x3, void* stream) {
   SIU3R_CHECK(shapes_host, "msdeform_sample: null pointer");
   SIU3R_CHECK(L >= 1 && L <= 4 && d % 4 == 0, "msdeform_sample: L=%d (1..4), d=%d (%%4)", L, d);
   MsdShapes sh;
@@ -936,10 +974,13 @@ extern "C" int siu3r_msdeform_sample(const void* value, int v_dtype, const float
   SIU3R_CHECK(value && offs_aw && ref && out, "msdeform_sample: null pointer");
   SIU3R_CHECK(al4(value, v_dtype) && al4(out, out_dtype), "msdeform_sample: value, out must be 16-byte (fp32) / 8-byte (bf16) aligned");
   const int D4 = d / 4;
-  const int qb = (256 % D4 == 0) ? 256 / D4 : 0;  // queries per workgroup (0: the flat thread order)
+  // queries per workgroup (0: the flat thread order; planes with d % 8 != 0 take it, so that a lane pair is 8 consecutive columns)
+  const int qb = (256 % D4 == 0 && !(out_x3 && d % 8 != 0)) ? 256 / D4 : 0;
   const dim3 grid = qb ? dim3((unsigned)((int64_t)B * ((Q + qb - 1) / qb) * heads)) : grid1d((int64_t)B * Q * heads * D4);
   const bool al = (((uintptr_t)offs_aw) & 15) == 0 && P == 4;  // (rows of heads * L * 4 * 3 floats: every head's slice is 16-byte aligned)
-#define SIU3R_MSD(LT_, PT_) hipLaunchKernelGGL((msdeform_kernel<LT_, PT_>), grid, dim3(256), 0, (hipStream_t)stream, value, v_dtype, offs_aw, ref, sh, out, out_dtype, B, S, Q, heads, d, L, P, qb)
+#define SIU3R_MSD(LT_, PT_) hipLaunchKernelGGL((msdeform_kernel<LT_, PT_>), grid, dim3(256), 0, (hipStream_t)stream, value, v_dtype, offs_aw, ref, sh, out, out_dtype, B, S, Q, heads, d, L, P, qb, out_x3)
+  SIU3R_CHECK(!out_x3 || (al && (L == 1 || L == 3 || L == 4) && ((uintptr_t)out & 127) == 0),
+              "msdeform_sample_planes: planes come from the <L, 4> kernels only (L = 1, 3, 4; P = 4; 16-byte aligned offs_aw) and need a 128-byte aligned destination");
   if (al && L == 1) SIU3R_MSD(1, 4);
   else if (al && L == 3) SIU3R_MSD(3, 4);
   else if (al && L == 4) SIU3R_MSD(4, 4);
@@ -947,6 +988,18 @@ extern "C" int siu3r_msdeform_sample(const void* value, int v_dtype, const float
 #undef SIU3R_MSD
   SIU3R_LAUNCH_CHECK("siu3r_msdeform_sample");
   return 0;
+}
+
+extern "C" int siu3r_msdeform_sample(const void* value, int v_dtype, const float* offs_aw, const float* ref,
+                                     const int32_t* shapes_host, void* out, int out_dtype, int B, int S, int Q,
+                                     int heads, int d, int L, int P, void* stream) {
+  return msdeform_sample(value, v_dtype, offs_aw, ref, shapes_host, out, out_dtype, B, S, Q, heads, d, L, P, 0, stream);
+}
+
+extern "C" int siu3r_msdeform_sample_planes(const void* value, int v_dtype, const float* offs_aw, const float* ref, const int32_t* shapes_host,
+                                            void* out_planes, int B, int S, int Q, int heads, int d, int L, int P, void* stream) {
+  SIU3R_CHECK(d % 4 == 0 && ((int64_t)heads * d) % 32 == 0, "msdeform_sample_planes: planes need rows of whole 32-column segments (heads=%d, d=%d)", heads, d);
+  return msdeform_sample(value, v_dtype, offs_aw, ref, shapes_host, out_planes, SIU3R_F32, B, S, Q, heads, d, L, P, 1, stream);
 }
 
 extern "C" int siu3r_groupnorm(const void* x, int x_dtype, void* y, int y_dtype, const float* gamma,

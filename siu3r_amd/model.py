@@ -265,10 +265,14 @@ class AsymmetricCroCo:
         kvp = ops.Planes(qkv_buf, storage=qkv_buf) if (_KV_PLANES and ops.attention(qkv[:, :, 0], qkv[:, :, 1], qkv[:, :, 2], dry_run=True, **att)) else None
         ops.linear(x, ctx.w.linear_ln(p + ".attn.qkv", p + ".norm1"), ln=xs, a_planes=xp, rope=(rope[0], rope[1], pos, 2 * Cc), out=qkv_buf,
                    planes_out=kvp, planes_from_col=Cc)
-        a = ops.attention(qkv[:, :, 0], qkv[:, :, 1], qkv[:, :, 2], kv_planes=kvp is not None and kvp.valid, **att)
         x1, s1, _ = self._new_stream(x)
         xp1 = ops.Planes(x1)
-        ops.linear(a, ctx.w.linear(p + ".attn.proj"), residual=x, out=x1, stats_out=s1, planes_out=xp1)
+        # the attention output feeds proj only: written as planes when proj's plan reads them
+        wp = ctx.w.linear(p + ".attn.proj")
+        a = torch.empty((Z, N, Cc), dtype=torch.float32, device=x.device)
+        ap = _feeds_planes("enc_attn", ctx, a, lambda t: ops.linear(t, wp, residual=x, out=x1, stats_out=s1, planes_out=xp1, dry_run=True))
+        ops.attention(qkv[:, :, 0], qkv[:, :, 1], qkv[:, :, 2], kv_planes=kvp is not None and kvp.valid, out=a, planes_out=ap, planes_only=True, **att)
+        ops.linear(a, wp, residual=x, out=x1, stats_out=s1, a_planes=ap, planes_out=xp1)
         x2, s2, _ = self._new_stream(x)
         xp2 = ops.Planes(x2)
         w1, w2 = ctx.w.linear_ln(p + ".mlp.fc1", p + ".norm2"), ctx.w.linear(p + ".mlp.fc2")
@@ -417,28 +421,43 @@ class AsymmetricCroCo:
             kvp = ops.Planes(pj_buf, storage=pj_buf) if (ctx.split and _KV_PLANES and ops.attention(pj[:, :, 0], pj[:, :, 1], pj[:, :, 3], dry_run=True, **att)) else None
             ops.linear_grouped(A(x, xb), grp("qkvx", build), ln=xs, rope=(rope[0], rope[1], pos, 3 * Cc), out=pj_buf, planes_out=kvp, planes_from_col=Cc)
             kvp = kvp is not None and kvp.valid
-            a = ops.attention(pj[:, :, 0], pj[:, :, 1], pj[:, :, 3], kv_planes=kvp, **att)
+            self_qkv = (pj[:, :, 0], pj[:, :, 1], pj[:, :, 3])
         else:
-            pj = None
+            pj, kvp = None, False
+            att = dict(heads=DEC_HEADS, head_dim=hd, scale=hd ** -0.5, split3=ctx.split)
             qkv = ops.linear_grouped(A(x, xb), grp("qkv", lambda q: W_.linear_ln(q + ".attn.qkv", q + ".norm1")), out_dtype=ctx.act, ln=xs,
                                      rope=(rope[0], rope[1], pos, 2 * Cc)).view(B * V, N + 1, 3, DEC_HEADS, hd)
-            a = ops.attention(qkv[:, :, 0], qkv[:, :, 1], qkv[:, :, 2], heads=DEC_HEADS, head_dim=hd, scale=hd ** -0.5, split3=ctx.split)
-        x1, s1, b1 = self._new_stream(x)
-        ops.linear_grouped(a.view(B, V, N + 1, Cc), grp("proj", lambda q: W_.linear(q + ".attn.proj")), residual=x, out=x1, stats_out=s1, aux_out=b1)
+            self_qkv = (qkv[:, :, 0], qkv[:, :, 1], qkv[:, :, 2])
+
+        def attend(tag, wname, qkv_, res, S_out, **kw):
+            """attention -> its grouped projection (+ residual) into the stream S_out = (x, stats, bf16 copy).  bf16x3: the attention output
+            feeds that projection only -- written as planes when the launch's plan reads them, as in the encoder block"""
+            xo, so, bo = S_out
+            wp = grp(tag, lambda q: W_.linear(q + wname))
+            a4 = torch.empty((B, V, N + 1, Cc), dtype=ctx.act, device=x.device)
+            ap = _feeds_planes("dec_attn", ctx, a4, lambda t: ops.linear_grouped(t, wp, residual=res, out=xo, stats_out=so, aux_out=bo, dry_run=True))
+            ops.attention(*qkv_, out=a4.view(B * V, N + 1, Cc), planes_out=ap, planes_only=True, **att, **kw)
+            ops.linear_grouped(a4, wp, residual=res, out=xo, stats_out=so, aux_out=bo, a_planes=ap)
+
+        S1 = x1, s1, b1 = self._new_stream(x)
+        attend("proj", ".attn.proj", self_qkv, x, S1, kv_planes=kvp)
         qq = ops.linear_grouped(A(x1, b1), grp("projq", lambda q: W_.linear_ln(q + ".cross_attn.projq", q + ".norm2")), out_dtype=ctx.act, ln=s1,
                                 rope=(rope[0], rope[1], pos, Cc)).view(B * V, N + 1, DEC_HEADS, hd)
+        S2 = x2, s2, b2 = self._new_stream(x)
         if pj is not None:
             # side g's memory was projected from side (1 - g)'s rows: batch item b ^ 1 of the merged projection
-            a = ops.attention(qq, pj[:, :, 2], pj[:, :, 4], kv_bxor=1, kv_planes=kvp, **att)
+            attend("xproj", ".cross_attn.proj", (qq, pj[:, :, 2], pj[:, :, 4]), x1, S2, kv_bxor=1, kv_planes=kvp)
         else:
             kv = ops.linear_grouped(A(x, xb), grp("projkv", lambda q: W_.linear_ln([q + ".cross_attn.projk", q + ".cross_attn.projv"], q + ".norm_y")),
                                     out_dtype=ctx.act, ln=xs, flip=True, rope=(rope[0], rope[1], pos, Cc)).view(B * V, N + 1, 2, DEC_HEADS, hd)
-            a = ops.attention(qq, kv[:, :, 0], kv[:, :, 1], heads=DEC_HEADS, head_dim=hd, scale=hd ** -0.5, split3=ctx.split)
-        x2, s2, b2 = self._new_stream(x)
-        ops.linear_grouped(a.view(B, V, N + 1, Cc), grp("xproj", lambda q: W_.linear(q + ".cross_attn.proj")), residual=x1, out=x2, stats_out=s2, aux_out=b2)
-        h = ops.linear_grouped(A(x2, b2), grp("fc1", lambda q: W_.linear_ln(q + ".mlp.fc1", q + ".norm3")), out_dtype=ctx.act, act=ACT_GELU, ln=s2)
-        ops.linear_grouped(h, grp("fc2", lambda q: W_.linear(q + ".mlp.fc2")), residual=x2, out=d["g"][i + 1], stats_out=d["gstat"][i + 1],
-                           aux_out=d["gb16"][i + 1])
+            attend("xproj", ".cross_attn.proj", (qq, kv[:, :, 0], kv[:, :, 1]), x1, S2)
+        # fc1's GELU output feeds fc2 only (bf16x3: planes in place of the fp32 values when fc2's plan reads them)
+        w1, w2 = grp("fc1", lambda q: W_.linear_ln(q + ".mlp.fc1", q + ".norm3")), grp("fc2", lambda q: W_.linear(q + ".mlp.fc2"))
+        out2 = dict(residual=x2, out=d["g"][i + 1], stats_out=d["gstat"][i + 1], aux_out=d["gb16"][i + 1])
+        h = torch.empty((B, V, N + 1, w1.n), dtype=ctx.act, device=x.device)
+        hp = _feeds_planes("dec_fc", ctx, h, lambda t: ops.linear_grouped(t, w2, dry_run=True, **out2))
+        ops.linear_grouped(A(x2, b2), w1, act=ACT_GELU, ln=s2, out=h, planes_out=hp, planes_only=True)
+        ops.linear_grouped(h, w2, a_planes=hp, **out2)
 
     def decode_side(self, d, i, side):
         """Layer i, side 0 = view 0 (dec_blocks), side 1 = views 1..V-1 batched (dec_blocks2); reads layer i's input
@@ -622,17 +641,22 @@ class _DPTHeads:
             res = skip()
         return ops.conv2d(o, W(".conv2"), pad=1, out_dtype=ctx.act, residual=res)
 
-    def _fusion(self, q, x0, x1):
+    def _fusion(self, q, x0, x1, reader=None):
         """FeatureFusionBlock_custom.forward (dpt_block.py:198-237).  out_conv (1x1) commutes with the
-        align_corners=True bilinear x2 (both linear, weights sum to 1), so it runs at the low resolution."""
+        align_corners=True bilinear x2 (both linear, weights sum to 1), so it runs at the low resolution.
+        reader: (site, plan) of the ONE convolution that reads the result (see _feeds_planes): the resize then writes planes when that
+        convolution reads them, and the return value is (map, Planes | None)."""
         out = x0 if x1 is None else self._rcu(q + ".resConfUnit1", x1, extra=x0)
         out = self._rcu(q + ".resConfUnit2", out)
         lead, (hh, ww) = out.shape[:-3], out.shape[-3:-1]
         out = ops.linear(out.flatten(-3, -2), self._w("linear", q + ".out_conv"), out_dtype=self.ctx.act)
-        return ops.resize_bilinear(out.view(-1, hh, ww, out.shape[-1]), (2 * hh, 2 * ww), True).view(*lead, 2 * hh, 2 * ww, -1)
+        up = torch.empty((*lead, 2 * hh, 2 * ww, out.shape[-1]), dtype=out.dtype, device=out.device)
+        upp = _feeds_planes(reader[0], self.ctx, up, reader[1]) if reader is not None and _CONV_PLANES else None
+        ops.resize_bilinear(out.view(-1, hh, ww, out.shape[-1]), (2 * hh, 2 * ww), True, out=up.view(-1, 2 * hh, 2 * ww, up.shape[-1]), planes_out=upp, planes_only=True)
+        return up if reader is None else (up, upp)
 
-    def trunk(self, tokens: Sequence[torch.Tensor], H, W):
-        """tokens: per hooked layer [*lead, N, C] fp32 (strided view: the patch tokens)"""
+    def trunk(self, tokens: Sequence[torch.Tensor], H, W, reader=None):
+        """tokens: per hooked layer [*lead, N, C] fp32 (strided view: the patch tokens); reader: of path_1, as in _fusion"""
         ctx = self.ctx
         nh, nw = H // 16, W // 16
         layers = []
@@ -649,7 +673,7 @@ class _DPTHeads:
         path4 = self._fusion(s + ".refinenet4", layers[3], None)
         path3 = self._fusion(s + ".refinenet3", path4, layers[2])
         path2 = self._fusion(s + ".refinenet2", path3, layers[1])
-        return self._fusion(s + ".refinenet1", path2, layers[0])
+        return self._fusion(s + ".refinenet1", path2, layers[0], reader)
 
     def _head4_names(self):
         return tuple(q + ".dpt.head.4" for q in self.ps)
@@ -657,11 +681,15 @@ class _DPTHeads:
     def forward_pts3d(self, tokens, H, W):
         """PixelwiseTaskWithDPT.forward + postprocess 'exp' (dpt_head.py:113-120; postprocess.py:45-61) -> pts3d [*lead, H, W, 3]"""
         ctx = self.ctx
-        x = self.trunk(tokens, H, W)
-        x = ops.conv2d(x, self._w("conv", ".dpt.head.0"), pad=1, out_dtype=ctx.act)
+        # path_1 and the x2 of head.0's output have one reader each, a 3 x 3 convolution: planes when its plan reads them
+        w0, w2 = self._w("conv", ".dpt.head.0"), self._w("conv", ".dpt.head.2")
+        x, xp = self.trunk(tokens, H, W, reader=("pts_fusion", lambda t: ops.conv2d(t, w0, pad=1, dry_run=True)))
+        x = ops.conv2d(x, w0, pad=1, out_dtype=ctx.act, a_planes=xp)
         lead = x.shape[:-3]
-        x = ops.resize_bilinear(x.flatten(0, -4), (H, W), True).view(*lead, H, W, -1)
-        x = ops.conv2d(x, self._w("conv", ".dpt.head.2"), pad=1, out_dtype=ctx.act, act=ACT_RELU)
+        up = torch.empty((*lead, H, W, x.shape[-1]), dtype=x.dtype, device=x.device)
+        upp = _feeds_planes("pts_resize", ctx, up, lambda t: ops.conv2d(t, w2, pad=1, act=ACT_RELU, dry_run=True)) if _CONV_PLANES else None
+        ops.resize_bilinear(x.flatten(0, -4), (H, W), True, out=up.view(-1, H, W, up.shape[-1]), planes_out=upp, planes_only=True)
+        x = ops.conv2d(up, w2, pad=1, out_dtype=ctx.act, act=ACT_RELU, a_planes=upp)
         xyz = _head4(ctx, self._head4_names(), x.view(lead[0], len(self.ps), H * W, -1))
         if xyz is None:
             xyz = ops.linear(x.flatten(-3, -2), self._w("linear", ".dpt.head.4"), out_dtype=torch.float32)
@@ -755,14 +783,21 @@ class CroCoViTAdapter:
         fn = ctx.ln(p + ".feat_norm", feat, 1e-6)
         offs_aw = ops.linear(qn, ctx.w.merged(p + ".attn.offs_aw", [p + ".attn.sampling_offsets", p + ".attn.attention_weights"]), out_dtype=torch.float32)
         value = ops.linear(fn, ctx.w.linear(p + ".attn.value_proj"), out_dtype=ctx.act)
-        samp = ops.msdeform_sample(value, offs_aw, ref, [(h, w)], 16, 4, ctx.act)
-        c = ops.linear(samp, ctx.w.linear(p + ".attn.output_proj"), out_dtype=torch.float32, residual=c)
+        # the samples feed output_proj only, the depth-wise convolution's output fc2 only: planes when that GEMM's plan reads them
+        wo = ctx.w.linear(p + ".attn.output_proj")
+        samp = torch.empty((value.shape[0], offs_aw.shape[1], value.shape[2]), dtype=ctx.act, device=value.device)
+        sp = _feeds_planes("ext_msd", ctx, samp, lambda t: ops.linear(t, wo, residual=c, dry_run=True))
+        ops.msdeform_sample(value, offs_aw, ref, [(h, w)], 16, 4, ctx.act, out=samp, planes_out=sp, planes_only=True)
+        c = ops.linear(samp, wo, out_dtype=torch.float32, residual=c, a_planes=sp)
         f1 = ops.linear(ctx.ln(p + ".ffn_norm", c, 1e-6), ctx.w.linear(p + ".ffn.fc1"), out_dtype=ctx.act)
         wk = p + ".ffn.dwconv.dwconv"
         if wk + "#w9c" not in ctx.w.vec:
             ctx.w.vec[wk + "#w9c"] = ctx.w.t(wk + ".weight").reshape(-1, 9).t().contiguous()
-        f2 = ops.dwconv3x3_gelu(f1, ctx.w.vec[wk + "#w9c"], ctx.w.v(wk + ".bias"), h, w)
-        return ops.linear(f2, ctx.w.linear(p + ".ffn.fc2"), out_dtype=torch.float32, residual=c)
+        w2 = ctx.w.linear(p + ".ffn.fc2")
+        f2 = torch.empty_like(f1)
+        fp = _feeds_planes("ext_dw", ctx, f2, lambda t: ops.linear(t, w2, residual=c, dry_run=True))
+        ops.dwconv3x3_gelu(f1, ctx.w.vec[wk + "#w9c"], ctx.w.v(wk + ".bias"), h, w, out=f2, planes_out=fp, planes_only=True)
+        return ops.linear(f2, w2, out_dtype=torch.float32, residual=c, a_planes=fp)
 
     def spm(self, img8: torch.Tensor):
         """SpatialPriorModule + level embeddings (vit_adapter.py:380-391): needs only the image."""
@@ -1132,6 +1167,29 @@ class VideoMask2FormerForVideoSegmentation:
 # ==================================================================================================
 _KV_PLANES = not os.environ.get("SIU3R_NO_KV_PLANES")  # A/B: k / v written pre-split by the q | k | v projections (bf16x3)
 _CONV_PLANES = not os.environ.get("SIU3R_NO_CONV_PLANES")  # A/B: pre-split planes between the convolutions of the paired DPT heads
+# Producer kernels that are not GEMMs write pre-split planes when a bf16x3 GEMM is their only reader (attention -> proj, resize -> 3 x 3
+# convolution, deformable sampling -> output_proj, depth-wise convolution -> fc2; the grouped decoder fc1 -> fc2).  One name per site; a
+# site is on when it is listed here (DESIGN.md records what each measured), pre-split operands are not switched off (ops._NO_PRESPLIT; the
+# convolution sites: _CONV_PLANES as well) and the consumer's own plan reads planes.  SIU3R_PRODUCER_PLANES="site,site" overrides the list
+# ("" = none) for a same-board A/B of single sites.
+_PRODUCER_PLANES_SITES = ("enc_attn", "dec_attn", "dec_fc", "pts_resize", "pts_fusion", "ext_msd", "ext_dw")
+# off: the decoder's two sites -- the measured tile table (csrc/gemm_tuned.h) runs the grouped proj / xproj / fc2 of a
+# pair on the LDS-DMA kernel, which has no pre-split A operand, so their plans never read planes and asking them costs three plan queries
+# per layer -- and the adapter's two: alone the pairs gain 2.7 / 1.0 us, inside the step the slower sampler store eats it (+0.6 us per step
+# over the twelve launches), and the chain runs beside the encoder anyway.
+_PRODUCER_PLANES_DEFAULT = ("enc_attn", "pts_resize", "pts_fusion")
+_PRODUCER_PLANES = frozenset(s_ for s_ in os.environ.get("SIU3R_PRODUCER_PLANES", ",".join(_PRODUCER_PLANES_DEFAULT)).split(",") if s_)
+assert _PRODUCER_PLANES <= set(_PRODUCER_PLANES_SITES), _PRODUCER_PLANES
+
+
+def _feeds_planes(site: str, ctx, like: torch.Tensor, plan) -> Optional[ops.Planes]:
+    """Planes in place of the fp32 tensor `like` (the buffer a producer kernel is about to fill; nothing but one GEMM reads it) when the
+    site is on and that GEMM's plan -- plan(like): the consumer called with dry_run=True -- reads planes; else None: both sides keep fp32."""
+    if site not in _PRODUCER_PLANES or ops._NO_PRESPLIT or not ctx.split or like.dtype != torch.float32:
+        return None
+    return ops.Planes(like, storage=like) if plan(like).a_x3_ok else None
+
+
 _DEC_QKVX = not os.environ.get("SIU3R_NO_DEC_QKVX")  # A/B: the decoder's self-attention q | k | v and the other side's cross-attention k | v as one launch
 _HEAD_PAIRS = os.environ.get("SIU3R_NO_HEAD_PAIRS", "0") != "1"  # the two heads of a kind as grouped launches (V == 2, B == 1)
 _DEC_PER_LAYER = os.environ.get("SIU3R_DEC_PER_LAYER", "0") == "1"

@@ -435,10 +435,10 @@ def linear(x: torch.Tensor, pw: PackedWeight, *, out_dtype=torch.float32, act=AC
     planes_out whose storage IS `out`): a mixed output -- fp32 in columns [0, planes_from_col), planes behind them.
     A stacked weight (stack_packed) makes this linear_grouped(x [B, G, M, K], ...), which has the arguments it names."""
     if _groups(pw):
-        if relu_in or splitk or planes_only or dry_run or a_planes is not None:
-            raise RuntimeError("relu_in / splitk / a_planes / planes_only / dry_run are not available with a stacked weight (linear_grouped)")
+        if relu_in or splitk:
+            raise RuntimeError("relu_in / splitk are not available with a stacked weight (linear_grouped)")
         return linear_grouped(x, pw, out_dtype=out_dtype, act=act, residual=residual, out=out, rope=rope, ln=ln, stats_out=stats_out, aux_out=aux_out,
-                              planes_out=planes_out, planes_from_col=planes_from_col)
+                              a_planes=a_planes, planes_out=planes_out, planes_only=planes_only, dry_run=dry_run, planes_from_col=planes_from_col)
     _gpu(x, residual, out)
     assert x.shape[-1] == pw.k, (x.shape, pw.k)
     if out is None:
@@ -514,12 +514,15 @@ def _apply_planes(p: GemmParams, x, out, a_planes, planes_out, planes_only, dry_
 
 def linear_grouped(x: torch.Tensor, pw: PackedWeight, *, out_dtype=torch.float32, act=ACT_NONE, residual: Optional[torch.Tensor] = None,
                    out: Optional[torch.Tensor] = None, rope=None, ln: Optional[RowStats] = None, stats_out: Optional[RowStats] = None,
-                   aux_out: Optional[torch.Tensor] = None, flip: bool = False, planes_out: Optional[Planes] = None, planes_from_col: int = 0):
+                   aux_out: Optional[torch.Tensor] = None, flip: bool = False, a_planes: Optional[Planes] = None, planes_out: Optional[Planes] = None,
+                   planes_only: bool = False, dry_run: bool = False, planes_from_col: int = 0):
     """G weight sets in ONE launch: x [B, G, M, K] (strided, last dim contiguous) times pw = stack_packed([...G sets]) ->
     out [B, G, M, N]; group g of every batch item uses weight set g (blockIdx.z = b * G + g).  flip: group g reads the rows of
     group G-1-g of x (and their statistics) -- the cross-attention memory of a decoder side is the other view's tokens.
-    planes_out / planes_from_col: pre-split output columns, as in linear()."""
+    a_planes / planes_out / planes_only / dry_run / planes_from_col: pre-split operands, as in linear() (a_planes: not with flip)."""
     _gpu(x, residual, out)
+    if flip and a_planes is not None:
+        raise RuntimeError("linear_grouped: a_planes is not available with flip")
     G = pw.meta["groups"]
     assert x.dim() == 4 and x.shape[1] == G and x.shape[-1] == pw.k and x.stride(3) == 1, (x.shape, G, pw.k)
     B, _, M, _ = x.shape
@@ -541,7 +544,7 @@ def linear_grouped(x: torch.Tensor, pw: PackedWeight, *, out_dtype=torch.float32
     if rope is not None:
         _apply_rope(p, rope, B * G * M)
     _apply_ln_stats_aux(p, pw, x, out, p.lda, p.ldc, (p.sa, sa_i, p.sc, p.sc_i), ln, stats_out, aux_out, x_first=xf)
-    return _launch(p, x, out, planes_out=planes_out, planes_from_col=planes_from_col)
+    return _launch(p, x, out, a_planes, planes_out, planes_only, dry_run, planes_from_col)
 
 
 def bmm_nt(a: torch.Tensor, b_hi: torch.Tensor, b_lo: Optional[torch.Tensor], n: int, k: int, *, out_dtype=torch.float32,
@@ -674,18 +677,39 @@ def patch_embed(img: torch.Tensor, pw: PackedWeight, out: torch.Tensor, stats_ou
 _ATTN_SPLITKV = os.environ.get("SIU3R_NO_ATTN_SPLITKV", "0") != "1"
 
 
+def _producer_planes(planes_out: Optional[Planes], planes_only: bool, out: torch.Tensor, ok) -> bool:
+    """planes_out / planes_only of a kernel that is not a GEMM (attention, resize_bilinear, msdeform_sample, dwconv3x3_gelu): such a
+    kernel has ONE destination, so planes are written INSTEAD of the fp32 values (planes_only=True is required; `out` stays untouched,
+    unless it is the planes' storage) -- when `ok()` (the kernel has the planes form for this call) and pre-split operands are not
+    switched off; planes_out.valid / .only say so afterwards.  The caller asks the CONSUMER's plan first (dry_run=True -> a_x3_ok)
+    and passes planes_out only when it reads planes.  Returns whether the planes form runs."""
+    if planes_out is None:
+        return False
+    if not planes_only:
+        raise RuntimeError("a producer kernel writes planes INSTEAD of fp32 values: planes_out needs planes_only=True")
+    # (same bytes, row for row: the planes may carry other leading dimensions than the kernel's output, e.g. [B, G, ...] against [B * G, ...])
+    assert planes_out.t.is_contiguous() and out.is_contiguous() and planes_out.t.numel() == out.numel() and planes_out.t.shape[-1] == out.shape[-1]
+    planes_out.valid = planes_out.only = (not _NO_PRESPLIT) and out.dtype == torch.float32 and bool(ok())
+    return planes_out.valid
+
+
 def attention(q, k, v, *, heads: int, head_dim: int, scale: float, rope=None, qpos=None, kpos=None,
               mask: Optional[torch.Tensor] = None, split3=False, kv_bxor: int = 0, kv_planes: bool = False, dry_run: bool = False,
-              plan: bool = False):
+              plan: bool = False, out: Optional[torch.Tensor] = None, planes_out: Optional[Planes] = None, planes_only: bool = False):
     """q [B,Nq,H,D] / k,v [B,Nk,H,D] strided views (D contiguous) -> out [B,Nq,H*D].  kv_bxor: batch item b attends to the keys / values
     of batch item b ^ kv_bxor (siu3r_attn_params.kv_bxor).  kv_planes: k and v are views of PRE-SPLIT planes (a projection written with
     planes_from_col); dry_run: launch nothing, return whether this launch could read such planes (siu3r_attention_kv_x3_ok).
     plan: launch nothing, return the siu3r_attn_plan_t of this launch (siu3r_attention_plan: kernel name, queries per workgroup, key
-    ranges, combine pass), or raise what the launch would raise."""
-    _gpu(q, k, v, mask)
+    ranges, combine pass), or raise what the launch would raise.  out: optional contiguous destination.  planes_out / planes_only: the
+    output as pre-split planes for the projection GEMM that reads it (_producer_planes; siu3r_attn_params.out_x3: the pipelined bf16x3
+    kernel)."""
+    _gpu(q, k, v, mask, out)
     B, Nq = q.shape[0], q.shape[1]
     Nk = k.shape[1]
-    out = q if dry_run or plan else torch.empty((B, Nq, heads * head_dim), dtype=q.dtype, device=q.device)  # (a dry run only needs a non-null pointer)
+    if out is None:
+        out = q if dry_run or plan else torch.empty((B, Nq, heads * head_dim), dtype=q.dtype, device=q.device)  # (a dry run only needs a non-null pointer)
+    else:
+        assert out.shape == (B, Nq, heads * head_dim) and out.dtype == q.dtype and out.is_contiguous()
     p = AttnParams()
     p.q, p.k, p.v, p.out = _p(q), _p(k), _p(v), _p(out)
     p.dtype = _dt(q)
@@ -726,6 +750,15 @@ def attention(q, k, v, *, heads: int, head_dim: int, scale: float, rope=None, qp
         pl = _lib.AttnPlan()
         check(_lib.lib().siu3r_attention_plan(C.byref(p), C.byref(pl)))
         return pl
+
+    def planes_ok():  # (asked with the planes' pointer: its alignment is part of the answer)
+        p.out = _p(planes_out.t)
+        ok = bool(_lib.lib().siu3r_attention_out_x3_ok(C.byref(p)))
+        p.out = _p(out)
+        return ok
+
+    if _producer_planes(planes_out, planes_only, out, planes_ok):
+        p.out, p.out_x3 = _p(planes_out.t), 1
     check(_lib.lib().siu3r_attention(C.byref(p), _stream()))
     return out
 
@@ -883,14 +916,20 @@ def _batch_strided(t: torch.Tensor, inner: int) -> int:
 
 
 def resize_bilinear(x: torch.Tensor, size, align_corners: bool, *, addend=None, ch_scale=None, ch_shift=None,
-                    out_dtype=None):
+                    out_dtype=None, out: Optional[torch.Tensor] = None, planes_out: Optional[Planes] = None, planes_only: bool = False):
     """x [N,IH,IW,C] / addend [N,OH,OW,C]: dense, or views whose batch items are dense but lie further apart (token maps cut out of a
-    longer per-item sequence are read in place)."""
-    _gpu(x, addend)
+    longer per-item sequence are read in place).  out: optional contiguous destination.  planes_out / planes_only: the plain resize (no
+    addend / ch_scale) with C % 32 == 0 writes pre-split planes for the convolution that reads it (_producer_planes)."""
+    _gpu(x, addend, out)
     N, IH, IW, Cc = x.shape
     OH, OW = size
-    out = torch.empty((N, OH, OW, Cc), dtype=out_dtype or x.dtype, device=x.device)
+    if out is None:
+        out = torch.empty((N, OH, OW, Cc), dtype=out_dtype or x.dtype, device=x.device)
+    assert out.shape == (N, OH, OW, Cc) and out.is_contiguous()
     x_bs = _batch_strided(x, IH * IW * Cc)
+    if _producer_planes(planes_out, planes_only, out, lambda: addend is None and ch_scale is None and Cc % 32 == 0 and planes_out.t.data_ptr() % 128 == 0):
+        check(_lib.lib().siu3r_resize_bilinear_planes(_p(x), _dt(x), _p(planes_out.t), N, IH, IW, OH, OW, Cc, int(align_corners), x_bs, _stream()))
+        return out
     a_bs = OH * OW * Cc
     if addend is not None:
         assert addend.shape == out.shape
@@ -946,28 +985,43 @@ def lpips_layer(f0: torch.Tensor, f1: torch.Tensor, w: torch.Tensor, eps: float)
     return dist
 
 
-def dwconv3x3_gelu(x: torch.Tensor, w9c: torch.Tensor, bias: torch.Tensor, H: int, W: int):
-    _gpu(x)
+def dwconv3x3_gelu(x: torch.Tensor, w9c: torch.Tensor, bias: torch.Tensor, H: int, W: int, *, out: Optional[torch.Tensor] = None,
+                   planes_out: Optional[Planes] = None, planes_only: bool = False):
+    """out / planes_out / planes_only: as in resize_bilinear (fp32 x, C % 32 == 0)"""
+    _gpu(x, out)
     assert x.is_contiguous()
     B, N, Cc = x.shape
     assert N == 21 * (H * W // 4)
-    out = torch.empty_like(x)
+    if out is None:
+        out = torch.empty_like(x)
+    assert out.shape == x.shape and out.dtype == x.dtype and out.is_contiguous()
+    if _producer_planes(planes_out, planes_only, out, lambda: x.dtype == torch.float32 and Cc % 32 == 0 and planes_out.t.data_ptr() % 128 == 0):
+        check(_lib.lib().siu3r_dwconv3x3_gelu_planes(_p(x), _p(planes_out.t), _p(w9c), _p(bias), B, H, W, Cc, _stream()))
+        return out
     check(_lib.lib().siu3r_dwconv3x3_gelu(_p(x), _p(out), _dt(x), _p(w9c), _p(bias), B, H, W, Cc, _stream()))
     return out
 
 
 def msdeform_sample(value: torch.Tensor, offs_aw: torch.Tensor, ref: torch.Tensor, shapes: Sequence[Sequence[int]],
-                    heads: int, points: int, out_dtype):
-    """value [B,S,heads*d]; offs_aw fp32 [B,Q,heads*L*P*3]; ref fp32 [Q,L,2] -> [B,Q,heads*d]."""
-    _gpu(value, offs_aw, ref)
+                    heads: int, points: int, out_dtype, *, out: Optional[torch.Tensor] = None, planes_out: Optional[Planes] = None,
+                    planes_only: bool = False):
+    """value [B,S,heads*d]; offs_aw fp32 [B,Q,heads*L*P*3]; ref fp32 [Q,L,2] -> [B,Q,heads*d].  out / planes_out / planes_only: as in
+    resize_bilinear (the kernels specialised for 1, 3 or 4 levels of 4 points; heads * d % 32 == 0)."""
+    _gpu(value, offs_aw, ref, out)
     assert value.is_contiguous() and offs_aw.is_contiguous() and ref.is_contiguous() and offs_aw.dtype == torch.float32
     B, S, Cc = value.shape
     Q = offs_aw.shape[1]
     L = len(shapes)
     d = Cc // heads
     assert offs_aw.shape[2] == heads * L * points * 3 and ref.shape == (Q, L, 2)
-    out = torch.empty((B, Q, Cc), dtype=out_dtype, device=value.device)
+    if out is None:
+        out = torch.empty((B, Q, Cc), dtype=out_dtype, device=value.device)
+    assert out.shape == (B, Q, Cc) and out.is_contiguous()
     arr = (C.c_int32 * (2 * L))(*[int(v) for s in shapes for v in s])
+    if _producer_planes(planes_out, planes_only, out, lambda: L in (1, 3, 4) and points == 4 and Cc % 32 == 0 and offs_aw.data_ptr() % 16 == 0
+                        and planes_out.t.data_ptr() % 128 == 0):
+        check(_lib.lib().siu3r_msdeform_sample_planes(_p(value), _dt(value), _p(offs_aw), _p(ref), arr, _p(planes_out.t), B, S, Q, heads, d, L, points, _stream()))
+        return out
     check(_lib.lib().siu3r_msdeform_sample(_p(value), _dt(value), _p(offs_aw), _p(ref), arr, _p(out), _dt(out), B, S, Q,
                                            heads, d, L, points, _stream()))
     return out
