@@ -658,6 +658,36 @@ int siu3r_mcmc_noise(float* means, const float* log_scales, const float* quats_x
 int siu3r_mcmc_regularize(const float* logit_opacity, const float* log_scales, int64_t G, float lambda_o, float lambda_s, float* grad_opacity,
                           float* grad_scales, void* ws, float* value, void* stream);
 
+/* ---- the cameras of splat refinement (csrc/camera.hip): per-view exposure and one fused pose / exposure step ----
+ * Exposure.  out[v,c,p] = sum_k M[v,c,k] in[v,k,p] + M[v,c,3]: M [V,3,4] fp32 on the device, `in` fp32 images of V views x 3 channels x
+ * H x W pixels read AS STORED through four ELEMENT strides (view, channel, row, column; a host array of 4, >= 0) as siu3r_photo_loss reads
+ * its images, `out` contiguous [V,3,H,W].  An identity M returns the bits of a finite input (a -0 comes back as +0). */
+int siu3r_exposure_apply(const float* in, const int64_t* in_strides, const float* M, int V, int H, int W, float* out, void* stream);
+/* Backward from g_out (contiguous [V,3,H,W]); either output may be NULL (both NULL: nothing is launched).
+ * g_in[v,k,p] = sum_c M[v,c,k] g_out[v,c,p], in in's layout (same strides; every pixel is written; the layout must not overlap itself).
+ * g_M [V,3,4]: g_M[v,c,k] = sum_p g_out[v,c,p] in[v,k,p], g_M[v,c,3] = sum_p g_out[v,c,p]: exact fp64 products, fixed-order fp64 sums (per
+ * workgroup, then the workgroups of a view in index order by a second launch), rounded once; ws: siu3r_exposure_ws(V, H, W) BYTES on the
+ * device, 8-byte aligned (0: the shape is not supported), needed for g_M only.  H * W < 2^31 - 2048, V <= 65535.  Deterministic: no
+ * atomics, two calls on equal inputs give equal bits.  Nothing allocates or synchronises with the host. */
+int64_t siu3r_exposure_ws(int V, int H, int W);
+int siu3r_exposure_apply_bwd(const float* in, const int64_t* in_strides, const float* M, const float* g_out, int V, int H, int W, float* g_in,
+                             float* g_M, void* ws, void* stream);
+/* Camera step: ONE launch, one thread per view, for the pose c2w [V,4,4] (camera-to-world, row-major) and the exposure M [V,3,4], both
+ * updated in place.  Either half may be absent: c2w and g_xi both NULL, or M and g_M both NULL.  g_xi [V,6] = (rho, theta) = (translation,
+ * rotation): the gradient of a LEFT perturbation of world->camera at 0, as the K2 backward returns it; g_M [V,3,4].
+ * exp_avg / exp_avg_sq [V,18]: the Adam moments, 6 of the pose then 12 of the exposure.  free_mask [V] uint8 (or NULL: every view): a view
+ * whose byte is 0 keeps the bits of c2w, M and its moments.  t >= 1: the caller's GLOBAL step count.
+ * Per element, in fp64 from the fp32 state and rounded to fp32 once per stored value, in the operation order of siu3r_gaussian_adam:
+ *   m = beta1 m + (1 - beta1) g;  v = beta2 v + ((1 - beta2) g) g;  step = ((lr / bc1) m) / (sqrt(v) / sqrt(bc2) + eps),  bc = 1 - beta^t
+ * with lr = lr_trans for rho, lr_rot for theta, lr_exposure for M (doubles: a host rate enters the fp64 arithmetic unrounded).  M -= step.  The pose variable is re-centred at 0 every step, so
+ * xi = -step, and the pose is folded as c2w <- c2w exp(-xi^) (w2c <- exp(xi^) w2c), the exponential in closed form:
+ *   exp(u^) = [R t; 0 1],  R = I + A K + B K^2,  t = (I + B K + C K^2) rho,  K = theta^,  th = |theta|,
+ *   A = sin th / th,  B = (1 - cos th) / th^2,  C = (th - sin th) / th^3, each by its three-term series below th = 1e-2.
+ * A free view whose six steps are exactly 0 (zero gradient and moments, eps > 0) keeps the bits of c2w.  R is not re-orthonormalised.
+ * Elementwise and deterministic; nothing allocates or synchronises with the host.  Errors: siu3r_last_error(). */
+int siu3r_camera_step(float* c2w, const float* g_xi, float* M, const float* g_M, float* exp_avg, float* exp_avg_sq, const uint8_t* free_mask, int V,
+                      int64_t t, double lr_trans, double lr_rot, double lr_exposure, double beta1, double beta2, double eps, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -184,7 +184,11 @@ SIGNATURES = {
     "siu3r_mcmc_copy_rows": [_P, _P, _P, _I, _L, _P, _P, _L, _L, _P],
     "siu3r_mcmc_noise": [_P, _P, _P, _P, _P, _L, _F, _F, _P],
     "siu3r_mcmc_regularize": [_P, _P, _L, _F, _F, _P, _P, _P, _P, _P],
-    "siu3r_lift_ids": [_P, _I, _I, _I, _I, _I, _F, _I, C.c_uint32, _P, _P, _P, _P, _P],
+    "siu3r_exposure_ws": [_I, _I, _I],
+    "siu3r_exposure_apply": [_P, C.POINTER(C.c_int64), _P, _I, _I, _I, _P, _P],
+    "siu3r_exposure_apply_bwd": [_P, C.POINTER(C.c_int64), _P, _P, _I, _I, _I, _P, _P, _P, _P],
+    "siu3r_camera_step": [_P, _P, _P, _P, _P, _P, _P, _I, _L] + [C.c_double] * 6 + [_P],
+    "siu3r_lift_ids":[_P, _I, _I, _I, _I, _I, _F, _I, C.c_uint32, _P, _P, _P, _P, _P],
     "siu3r_panoptic_stage1": [_P] * 20 + [_I] * 9 + [_F, _F, _F, C.c_uint32, _P],
     "siu3r_panoptic_qcl": [_P, _P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P],
 }
@@ -194,6 +198,7 @@ _RESTYPES["siu3r_density_plan_ws"] = C.c_int64
 _RESTYPES["siu3r_depth_loss_ws"] = C.c_int64
 _RESTYPES["siu3r_gaussian_adam_ws"] = C.c_int64
 _RESTYPES["siu3r_mcmc_ws"] = C.c_int64
+_RESTYPES["siu3r_exposure_ws"] = C.c_int64
 
 _lib = None
 

@@ -8,6 +8,7 @@ only a layout the kernel's four strides cannot express (an expanded dimension of
 
 `depth_loss` is the depth term of the same refinement (csrc/depth_loss.hip): weighted L1 or per-view Pearson correlation of the K2 render's
 depth / opacity against a target depth, value and the gradients w.r.t. both render outputs from one call.
+`apply_exposure` is the per-view affine colour transform of camera optimisation (csrc/camera.hip), differentiable w.r.t. the image and M.
 There is no CPU path and nothing here synchronises with the host."""
 from __future__ import annotations
 
@@ -247,3 +248,69 @@ def depth_loss(depth: torch.Tensor, opacity: torch.Tensor, target: torch.Tensor,
         out, per_view, valid, _, _ = _launch_depth(_as_vhw(depth), _as_vhw(opacity), _as_vhw(target), _as_vhw(weight), mode, space, min_opacity, False)
         loss = out[0]
     return (loss, per_view, valid) if return_terms else loss
+
+
+# ---- per-view exposure (csrc/camera.hip) -------------------------------------------------------------------------
+def _launch_exposure(img4: torch.Tensor, M3: torch.Tensor) -> torch.Tensor:
+    """One siu3r_exposure_apply call on a [V,3,H,W] view with arbitrary non-negative strides -> contiguous [V,3,H,W]"""
+    V, _, H, W = img4.shape
+    out = torch.empty((V, 3, H, W), dtype=torch.float32, device=img4.device)
+    with torch.cuda.device(img4.device):
+        check(_lib.lib().siu3r_exposure_apply(_p(img4), (C.c_int64 * 4)(*img4.stride()), _p(M3), V, H, W, _p(out), _stream()))
+    return out
+
+
+class _ApplyExposure(torch.autograd.Function):
+    """The two exposure kernels: the backward computes the gradients that are asked for, g_img in the image's stored layout."""
+
+    @staticmethod
+    def forward(ctx, img, M, channels_last):
+        i4 = _expressible(_as_vchw(img.detach(), channels_last), img.requires_grad)
+        M3 = M.detach().reshape(-1, 3, 4).contiguous()
+        ctx.save_for_backward(i4, M3)
+        ctx.channels_last, ctx.img_shape, ctx.m_shape = channels_last, img.shape, M.shape
+        return _launch_exposure(i4, M3)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_out):
+        i4, M3 = ctx.saved_tensors
+        want_img, want_m = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if not (want_img or want_m):
+            return None, None, None
+        lib = _lib.lib()
+        V, _, H, W = i4.shape
+        dev = i4.device
+        g_out = g_out.contiguous()
+        g_img = torch.empty_strided(tuple(i4.shape), tuple(i4.stride()), dtype=torch.float32, device=dev) if want_img else None
+        g_m = torch.empty((V, 3, 4), dtype=torch.float32, device=dev) if want_m else None
+        ws = torch.empty(int(lib.siu3r_exposure_ws(V, H, W)) // 8, dtype=torch.float64, device=dev) if want_m else None
+        with torch.cuda.device(dev):
+            check(lib.siu3r_exposure_apply_bwd(_p(i4), (C.c_int64 * 4)(*i4.stride()), _p(M3), _p(g_out), V, H, W, _p(g_img), _p(g_m), _p(ws), _stream()))
+        if want_img:
+            g_img = (g_img.permute(0, 2, 3, 1) if ctx.channels_last else g_img).reshape(ctx.img_shape)
+        return g_img, g_m.reshape(ctx.m_shape) if want_m else None, None
+
+
+def apply_exposure(img: torch.Tensor, M: torch.Tensor, channels_last: bool = False) -> torch.Tensor:
+    """Per-view affine colour transform out[v,c] = sum_k M[v,c,k] img[v,k] + M[v,c,3] of float32 GPU images with 3 channels: img [V,3,H,W]
+    (channels_last: [V,H,W,3]; a single image may drop V), read as stored; M [V,3,4] ([3,4] for a single image).  Returns a contiguous
+    [V,3,H,W] tensor, the layout photometric_loss then reads (V = 1 for a single image).  Differentiable w.r.t. `img` (the gradient comes
+    back in img's stored layout) and w.r.t. `M` (deterministic fixed-order sums); only the gradients that are needed are computed.  An
+    identity M returns the bits of the input.  There is no CPU path and nothing here synchronises with the host."""
+    for name, t in (("img", img), ("M", M)):
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name} must be a tensor, got {type(t).__name__}")
+    _gpu(img, M)
+    if img.dtype != torch.float32 or M.dtype != torch.float32:
+        raise ValueError(f"apply_exposure takes a float32 image and a float32 M, got {img.dtype} and {M.dtype}")
+    if img.dim() not in (3, 4) or img.numel() == 0 or img.shape[-1 if channels_last else -3] != 3:
+        raise ValueError(f"img must be [V,3,H,W], [V,H,W,3] with channels_last, or one such image without V, got {tuple(img.shape)}")
+    V = 1 if img.dim() == 3 else img.shape[0]
+    if tuple(M.shape) != (V, 3, 4) and not (img.dim() == 3 and tuple(M.shape) == (3, 4)):
+        raise ValueError(f"M must be [{V}, 3, 4] for an image batch {tuple(img.shape)}, got {tuple(M.shape)}")
+    if M.device != img.device:
+        raise ValueError(f"img is on {img.device}, M on {M.device}")
+    if torch.is_grad_enabled() and (img.requires_grad or M.requires_grad):
+        return _ApplyExposure.apply(img, M, channels_last)
+    return _launch_exposure(_as_vchw(img.detach(), channels_last), M.detach().reshape(-1, 3, 4).contiguous())

@@ -12,9 +12,10 @@ from typing import Dict, List, Optional, Sequence, Tuple, Union
 import torch
 
 from . import raster
+from .cameras import CameraControl, CameraState
 from .cuda_splatting import render_cuda
 from .density import FIELDS, DensityControl, DensityStats, densify_and_prune, scene_extent
-from .losses import DEPTH_MODES, DEPTH_SPACES, depth_loss, photometric_loss
+from .losses import DEPTH_MODES, DEPTH_SPACES, apply_exposure, depth_loss, photometric_loss
 from .mcmc import MCMCControl, event as mcmc_event, inject_noise, regularize
 from .optim import GaussianAdam, TorchAdam, log_linear, means_lr_schedule
 
@@ -120,7 +121,7 @@ def refine_gaussians(means, scales, rotations, opacities, harmonics, images, c2w
                      density: Union[DensityControl, MCMCControl, None] = None, depths=None, depth_weights=None, lambda_depth=0.0, depth_mode: str = "l1",
                      depth_space: str = "depth", depth_min_opacity: float = 0.5, optimizer: str = "torch", sparse: bool = False,
                      means_lr_final: Optional[float] = None, means_lr_extent_scale: bool = False,
-                     sh_rest_lr_scale: float = 1.0) -> Tuple[Dict[str, torch.Tensor], List[float]]:
+                     sh_rest_lr_scale: float = 1.0, cameras: Optional[CameraControl] = None) -> Tuple[Dict[str, torch.Tensor], List[float]]:
     """means [G,3], scales [G,3], rotations [G,4], opacities [G], harmonics [G,3,n] (n = (deg+1)^2): what `Gaussians` carries, on the GPU.
     images [V,3,H,W]: the posed target views; c2w [V,4,4] camera-to-world, Kn [V,3,3] (or [3,3]) normalised intrinsics, near / far floats
     (or [V]), bg 3 floats: render_cuda's conventions.
@@ -177,7 +178,20 @@ def refine_gaussians(means, scales, rotations, opacities, harmonics, images, c2w
     to this over `iters` (optim.means_lr_schedule);  means_lr_extent_scale=True multiplies both ends by the scene extent
     (density.scene_extent of the control when it names one, else density.scene_extent(c2w): one host read);  sh_rest_lr_scale steps the SH
     coefficients above DC at that fraction of the `harmonics` rate (3DGS: 0.05).  `density=` and the depth keywords work as above; the
-    returned dict gains "optimizer_steps", the optimiser's step count (== iters, also across density events)."""
+    returned dict gains "optimizer_steps", the optimiser's step count (== iters, also across density events).
+
+    cameras: a cameras.CameraControl also optimises the per-view pose and / or a per-view affine colour transform ("exposure"); None, the
+    default, is the loop above and returns the same bits as a call without the keyword.  With a control, every iteration from
+    control.start on renders with the current poses (a copy of `c2w` held by a cameras.CameraState; the caller's tensor is not modified)
+    and, when control.pose, with the state's gradient holders as cam_rot_delta / cam_trans_delta; when control.exposure the image goes
+    through losses.apply_exposure before photometric_loss (the depth term keeps reading the render's own depth and opacity).  After the
+    Gaussians' optimiser step the camera step runs: one fused launch (Adam and the se(3) retraction, csrc/camera.hip) whatever `optimizer`
+    says, its rates decayed by control.lr_final_scale over the iterations from control.start on.  The views of control.fixed keep the
+    bits of their pose and an exactly identity exposure.  `density=`, `depths=` and `sparse=` work unchanged; a classic control's scene
+    extent is still taken from the starting cameras.  params=() with a control is multi-view pose / exposure alignment against frozen
+    Gaussians (without a control params=() runs no iteration).  The returned dict gains "c2w" [V,4,4], "exposure" [V,3,4] (identity where
+    it is not optimised) and "camera_steps".  A control that moves nothing, a fixed index out of range, every view fixed and a
+    non-positive rate raise ValueError before any device work."""
     lambdas_depth = _check_depth_args(images, depths, depth_weights, lambda_depth, depth_mode, depth_space, depth_min_opacity, iters)
     hip = _check_optim_args(optimizer, sparse, means_lr_final, means_lr_extent_scale, sh_rest_lr_scale)
     params = tuple(params)
@@ -189,6 +203,8 @@ def refine_gaussians(means, scales, rotations, opacities, harmonics, images, c2w
         if k not in FIELDS:
             raise ValueError(f"lrs: unknown field {k!r} (one of {FIELDS})")
         lr[k] = float(v)
+    if cameras is not None:
+        cameras.validate(images.shape[0])
     budgeted = isinstance(density, MCMCControl)  # which of the two strategies a control is: said here, read where they differ
     if budgeted:
         density.validate(means.shape[0])
@@ -275,7 +291,16 @@ def refine_gaussians(means, scales, rotations, opacities, harmonics, images, c2w
         start.update({k: _FROM_PARAM[k](v) for k, v in frozen.items()})
         cov6_fixed = None if cov_moves else cov6_of()
 
-    for it in range(int(iters) if free else 0):
+    cam = cam_rates = None  # the cameras' state and their (lr_trans, lr_rot, lr_exposure) per iteration from cameras.start on
+    if cameras is not None and int(iters) > 0:
+        cam = CameraState(c2w, cameras.pose, cameras.exposure, cameras.fixed)
+        cam_rates = cameras.rates(int(iters))
+    for it in range(int(iters) if free or cam is not None else 0):
+        cam_on = cam is not None and it >= int(cameras.start)
+        if not (free or cam_on):
+            continue  # (frozen Gaussians before the cameras start: nothing moves)
+        if cam_on:
+            cam.zero_grad()
         if it in strategy.events:
             with torch.no_grad():
                 event(it)
@@ -284,12 +309,16 @@ def refine_gaussians(means, scales, rotations, opacities, harmonics, images, c2w
                 p = float(density.reset_opacity)
                 free["opacities"].clamp_(max=math.log(p / (1.0 - p)))
                 opt.zero_moments("opacities")
-        opt.zero_grad(set_to_none=True)
+        if opt is not None:
+            opt.zero_grad(set_to_none=True)
         cov6 = cov6_of() if cov_moves else cov6_fixed
-        rendered = render_cuda(c2w, Kn, near_t, far_t, (H, W), bg_t, value("means")[None].expand(V, -1, -1), cov6[None].expand(V, -1, -1),
+        pose_holders = dict(cam_rot_delta=cam.rot_delta, cam_trans_delta=cam.trans_delta) if cam_on and cam.pose else {}
+        rendered = render_cuda(cam.c2w if cam_on else c2w, Kn, near_t, far_t, (H, W), bg_t, value("means")[None].expand(V, -1, -1), cov6[None].expand(V, -1, -1),
                                value("harmonics")[None].expand(V, -1, -1, -1), value("opacities")[None].expand(V, -1),
-                               density_stats=strategy.stats, return_aux=want_aux)
+                               density_stats=strategy.stats, return_aux=want_aux, **pose_holders)
         img, dep = rendered[0], rendered[1]
+        if cam_on and cam.exposure:
+            img = apply_exposure(img, cam.M)
         opa = _aux_cat(rendered[2], "opacity") if lambdas_depth is not None else None
         radii = _aux_cat(rendered[2], "radii") if sparse else None
         if lambdas_depth is None:
@@ -302,7 +331,10 @@ def refine_gaussians(means, scales, rotations, opacities, harmonics, images, c2w
             reg = regularize(unc("opacities"), unc("scales"), strategy.reg_o, strategy.reg_s, free["opacities"].grad if strategy.reg_o > 0.0 else None,
                              free["scales"].grad if strategy.reg_s > 0.0 else None)
             loss = loss.detach() + reg.sum()
-        opt.step(visible=radii, lrs=None if means_lrs is None else {"means": means_lrs[it]})
+        if opt is not None:
+            opt.step(visible=radii, lrs=None if means_lrs is None else {"means": means_lrs[it]})
+        if cam_on:
+            cam.step(cam.step_count + 1, cam_rates[it - int(cameras.start)])
         if strategy.noise_lr > 0.0:
             scaler = strategy.noise_lr * (lr["means"] if means_lrs is None else means_lrs[it])
             noise = torch.randn((free["means"].shape[0], 3), generator=noise_gen, device=dev, dtype=torch.float32)
@@ -320,4 +352,8 @@ def refine_gaussians(means, scales, rotations, opacities, harmonics, images, c2w
             out["depth_losses"] = depth_losses
         if hip:
             out["optimizer_steps"] = opt.step_count if free else 0
+        if cameras is not None:
+            out["c2w"] = cam.c2w.clone() if cam is not None else c2w.clone()
+            out["exposure"] = cam.M.detach().clone() if cam is not None else torch.eye(3, 4, device=dev).repeat(V, 1, 1)
+            out["camera_steps"] = cam.step_count if cam is not None else 0
     return out, losses
