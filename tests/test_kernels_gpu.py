@@ -85,6 +85,7 @@ def test_gemm_rope_epilogue(mode):
     check(f"gemm_rope_epilogue[{name}]", out, ref, tol)
 
 
+# (per-element float64 parity of the next two kernels, their persistent tile loops included: tests/test_rowstream_gpu.py, dense_rowstream64.py)
 def test_proj_rows_x3_dedicated_kernel():
     """The heads' last 1 x 1 convolutions as row streams (csrc/proj.hip, siu3r_proj_rows_x3): two heads x two batch items, a ragged row
     count, 83 columns of 256 (rows of 83 floats) and 3 columns of 128 -- against fp32 torch and against the GEMM route it replaces."""
