@@ -365,7 +365,8 @@ int siu3r_raster_geometry(int width, int height, int64_t G, int32_t* out8);
  * (Gaussians.harmonics as stored), mode 1 unused; all shared by the V views) for every view.  cams_host: V structs in HOST memory,
  * copied to cams_dev (device, V * sizeof(siu3r_raster_cam) bytes) on the stream.  Outputs, all [V, G, ...]: rec fp32 [.,12] = {mean2d x, y,
  * depth, 0 | conic a, b, c, opacity | r, g, b, 0} (16-byte aligned), radii [.,2] i32, rect [.,4] i32 (tile rect [min,max)),
- * tiles_touched i32, keys u32 (depth bits; 0xffffffff = culled).  stats: u64 [V,4] = {visible Gaussians, tile pairs D, coarse
+ * tiles_touched i32, keys u32 (depth bits; 0xffffffff = culled; a Gaussian whose mean or covariance is not finite is culled in every
+ * view).  stats: u64 [V,4] = {visible Gaussians, tile pairs D, coarse
  * entries E (stage 3), flags: bit 0 entries overflowed cap_e, bit 1 tile lists overflowed cap_d}; zeroed here. */
 int siu3r_raster_project(const siu3r_raster_cam* cams_host, int V, void* cams_dev, int64_t G, const float* means, const float* cov,
                          int cov_stride, const float* opacities, const float* colors, int channels, int sh_planar, float* rec,

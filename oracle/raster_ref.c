@@ -183,6 +183,7 @@ static void project_one(const raster_cam* c, const float* mean, const float* cov
   c11 += blur;
   float det = c00 * c11 - c01 * c01;
   if (c->mode == 0 ? (det == 0.0f) : (det <= 0.0f)) return;
+  if (!(fabsf(det) <= 3.402823466e38f)) return;  /* a NaN mean or an Inf covariance takes no part (as project_kernel) */
   float det_inv = 1.0f / det;
   o->ca = c11 * det_inv;
   o->cb = -c01 * det_inv;

@@ -121,6 +121,9 @@ __global__ __launch_bounds__(256) void project_kernel(const Cam* __restrict__ ca
       const Cov2D p = project_cov2d(lens, V, tx, ty, tz, S);
       const float txz = p.txz, tyz = p.tyz, c00 = p.c00, c01 = p.c01, c11 = p.c11, det = p.det;
       if (c.mode == 0 ? (det == 0.0f) : (det <= 0.0f)) break;
+      // a NaN mean or an Inf covariance takes no part: a NaN determinant passes both tests above, and an infinite radius converts to
+      // INT_MAX, i.e. a rect over the whole frame with a NaN conic, which the composites blend at alpha_max on every pixel
+      if (!(fabsf(det) <= 3.402823466e38f)) break;
       const float det_inv = 1.0f / det;
       ca = c11 * det_inv;
       cb = -c01 * det_inv;

@@ -58,6 +58,7 @@ import pytest
 import torch
 
 import dense_raster_bwd64 as B
+import dense_raster_fwd64 as F
 from test_raster_stages_gpu import SENT, _Guarded
 
 pytestmark = pytest.mark.gpu
@@ -293,13 +294,13 @@ def _run_composite_bwd(kind, V, G, H, W, Cc, T, st, totals, ups):
     return grad, g_feats, qcnt
 
 
-def _check_composite(name, kind, Cc, refs, low, totals, grad, g_feats):
-    out, _, alpha = totals
-    for v, r in enumerate(refs):  # the state is the one the reference walked: the forward's maps are its float64 totals
-        keep = torch.from_numpy(~low[v])  # (a pixel below the margin may blend one entry more or less)
-        d_out = (out[v].cpu().double() - torch.from_numpy(r["out"])).abs()
-        assert float((d_out.permute(1, 2, 0) if kind == "k2" else d_out)[keep].max()) <= 1e-4 * max(1.0, float(np.abs(r["out"]).max()))
-        assert float((alpha[v].cpu().double() - torch.from_numpy(r["alpha"])).abs()[keep].max()) <= 1e-4
+def _check_composite(name, kind, Cc, refs, low, totals, grad, g_feats, case):
+    # the state is the one the reference walked: the forward's maps (the backward's saved totals), depth included, are held element by
+    # element to the derived forward bound of tests/dense_raster_fwd64.py (a pixel below the margin may blend one entry more or less)
+    out, depth, alpha = totals
+    o = out.cpu().numpy()
+    F.check_maps(f"{name} forward", kind, F.comp_fwd_ref(case, Cc if kind == "feat" else None), o.transpose(0, 2, 3, 1) if kind == "k2" else o, alpha.cpu().numpy(),
+                 depth.cpu().numpy() if kind == "k2" else None)
     got = grad.t.cpu()
     for v, r in enumerate(refs):
         _close(got[v], r["grad"], r["S"], r["bound"], f"{name} view {v} grad", r["chain"])
@@ -325,7 +326,7 @@ def test_composite_backward(name, mode):
         assert {0, 1, 31, 32, 33}.issubset(lens) and max(lens) > 64, sorted(lens)
         ql = B.quadrant_lists_ref(c["cams"][0], c["rec"][0], c["lists"][0])
         assert qcnt[0, 3 * 6 + 3, 0] == len(ql[(3 * 6 + 3, 0)]) >= 40, "the slivers are not on the quadrant's list"
-    _check_composite(f"{name} {mode}", kind, Cc, refs, low, totals, grad, g_feats)
+    _check_composite(f"{name} {mode}", kind, Cc, refs, low, totals, grad, g_feats, c)
 
 
 @pytest.mark.parametrize("kind", ["k2", "k3", "feat"])
@@ -367,7 +368,7 @@ def test_composite_backward_on_the_state_of_a_real_forward(kind):
     assert low.reshape(V, -1).mean(1).max() <= B.ZERO_SHARE_CAP, "more than 1 % of a view's pixels are zeroed"
     assert kind != "k2" or sum(r["counts"]["clamped"] for r in refs) > 0, "no alpha on the clamp"
     grad, g_feats, _ = _run_composite_bwd(kind, V, G, H, W, Cc, geo["T"], st, totals, ups)
-    _check_composite(f"forward_{kind}", kind, Cc, refs, low, totals, grad, g_feats)
+    _check_composite(f"forward_{kind}", kind, Cc, refs, low, totals, grad, g_feats, case)
 
 
 # ---- viewer helpers ---------------------------------------------------------------------------------------------------------------------

@@ -39,6 +39,7 @@ def _check_lists(st, ref):
     assert np.array_equal(st["ids"].cpu().numpy()[: ref["D"]], ref["ids"]), "per-tile sorted Gaussian lists differ"
 
 
+# (the oracle tests below compare by a global maximum on random scenes; per element against float64, branch by branch: test_raster_fwd_stages_gpu.py, dense_raster_fwd64.py)
 @pytest.mark.parametrize("shape", [(192, 256), (190, 250)], ids=["192x256", "ragged190x250"])
 @pytest.mark.parametrize("band4", [False, True], ids=["sh3", "sh4"])
 def test_k2_rgb_depth_ntouched(shape, band4):
