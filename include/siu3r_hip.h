@@ -689,6 +689,34 @@ int siu3r_exposure_apply_bwd(const float* in, const int64_t* in_strides, const f
 int siu3r_camera_step(float* c2w, const float* g_xi, float* M, const float* g_M, float* exp_avg, float* exp_avg_sq, const uint8_t* free_mask, int V,
                       int64_t t, double lr_trans, double lr_rot, double lr_exposure, double beta1, double beta2, double eps, void* stream);
 
+/* ---- bilateral-grid appearance correction of splat refinement (csrc/bilagrid.hip) ----
+ * grids [V,12,L,Gh,Gw] fp32 on the device: per view a grid of 3 x 4 colour matrices, channel 4c + k = entry (c, k); 2 <= L <= 16,
+ * 2 <= Gh, Gw <= 1024.  Slice: for pixel (y, x) of view v with colour p = (r, g, b),
+ *   lum = 0.299 r + 0.587 g + 0.114 b,  fx = (x + 0.5) / W * (Gw - 1),  fy = (y + 0.5) / H * (Gh - 1),  fz = clamp(lum, 0, 1) * (L - 1),
+ *   x0 = min(floor(fx), Gw - 2), tx = fx - x0 (likewise y, z),  M = the trilinear interpolation of the 8 corner matrices by nested
+ *   a + t (b - a) steps (one fma each; x, then y, then z),  out[c] = M[c,0] r + M[c,1] g + M[c,2] b + M[c,3].
+ * `in` is read AS STORED through four ELEMENT strides (view, channel, row, column; a host array of 4, >= 0) as siu3r_exposure_apply reads
+ * its images, `out` is contiguous [V,3,H,W].  The identity grid (channels 0, 5, 10 one, the rest zero) returns the bits of a finite input
+ * (a -0 comes back as +0); a NaN pixel gives a NaN output pixel and touches no other.  H * W < 2^31 - 2048, H, W <= 2^22, V <= 65535. */
+int siu3r_bilagrid_apply(const float* in, const int64_t* in_strides, const float* grids, int V, int H, int W, int L, int Gh, int Gw, float* out,
+                         void* stream);
+/* Backward from g_out (contiguous [V,3,H,W]); either output may be NULL (both NULL: nothing is launched).
+ * g_in, in in's layout (same strides; every pixel is written; the layout must not overlap itself):
+ *   g_in[k] = sum_c M[c,k] g_out[c] + lw[k] (L - 1) [0 < lum < 1] sum_c g_out[c] (dM/dz [c,:] . (r, g, b, 1)),
+ * dM/dz the xy-interpolated level z0 + 1 minus the xy-interpolated level z0; a clamped luminance gets no guidance gradient and the kink at an
+ * integer fz is held constant (the kernel's own z0 decides).
+ * g_grids [V,12,L,Gh,Gw], every element written: g_grids[v,4c+k,z,y,x] = sum over pixels of w_z w_y w_x g_out[c] (p_k or 1), gathered per
+ * vertex in a fixed order (fp32 per thread, an fp64 tree per workgroup): no atomics, two calls on equal inputs give equal bits; a vertex no
+ * pixel reaches gets exact zeros.  Nothing allocates or synchronises with the host. */
+int siu3r_bilagrid_apply_bwd(const float* in, const int64_t* in_strides, const float* grids, const float* g_out, int V, int H, int W, int L, int Gh,
+                             int Gw, float* g_in, float* g_grids, void* stream);
+/* Total variation: value[0] = (1/V) sum_v sum_{axis in z, y, x} mean((A[.. i+1 ..] - A[.. i ..])^2), the mean per view over the 12 channels and
+ * all positions of the differenced tensor: fp32 differences, fp64 products and fixed-order fp64 sums, rounded once.  g_grids (or NULL)
+ * ACCUMULATES scale * d tv / d grids.  ws: siu3r_bilagrid_tv_ws(V, L, Gh, Gw) BYTES on the device, 8-byte aligned (0: the shape is not
+ * supported).  Deterministic; nothing allocates or synchronises with the host. */
+int64_t siu3r_bilagrid_tv_ws(int V, int L, int Gh, int Gw);
+int siu3r_bilagrid_tv(const float* grids, int V, int L, int Gh, int Gw, float scale, float* g_grids, void* ws, float* value, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -188,6 +188,10 @@ SIGNATURES = {
     "siu3r_exposure_apply": [_P, C.POINTER(C.c_int64), _P, _I, _I, _I, _P, _P],
     "siu3r_exposure_apply_bwd": [_P, C.POINTER(C.c_int64), _P, _P, _I, _I, _I, _P, _P, _P, _P],
     "siu3r_camera_step": [_P, _P, _P, _P, _P, _P, _P, _I, _L] + [C.c_double] * 6 + [_P],
+    "siu3r_bilagrid_apply": [_P, C.POINTER(C.c_int64), _P, _I, _I, _I, _I, _I, _I, _P, _P],
+    "siu3r_bilagrid_apply_bwd": [_P, C.POINTER(C.c_int64), _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P],
+    "siu3r_bilagrid_tv_ws": [_I, _I, _I, _I],
+    "siu3r_bilagrid_tv": [_P, _I, _I, _I, _I, _F, _P, _P, _P, _P],
     "siu3r_lift_ids":[_P, _I, _I, _I, _I, _I, _F, _I, C.c_uint32, _P, _P, _P, _P, _P],
     "siu3r_panoptic_stage1": [_P] * 20 + [_I] * 9 + [_F, _F, _F, C.c_uint32, _P],
     "siu3r_panoptic_qcl": [_P, _P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P],
@@ -199,6 +203,7 @@ _RESTYPES["siu3r_depth_loss_ws"] = C.c_int64
 _RESTYPES["siu3r_gaussian_adam_ws"] = C.c_int64
 _RESTYPES["siu3r_mcmc_ws"] = C.c_int64
 _RESTYPES["siu3r_exposure_ws"] = C.c_int64
+_RESTYPES["siu3r_bilagrid_tv_ws"] = C.c_int64
 
 _lib = None
 

@@ -9,6 +9,7 @@ only a layout the kernel's four strides cannot express (an expanded dimension of
 `depth_loss` is the depth term of the same refinement (csrc/depth_loss.hip): weighted L1 or per-view Pearson correlation of the K2 render's
 depth / opacity against a target depth, value and the gradients w.r.t. both render outputs from one call.
 `apply_exposure` is the per-view affine colour transform of camera optimisation (csrc/camera.hip), differentiable w.r.t. the image and M.
+`apply_bilagrid` / `bilagrid_tv` are the per-view bilateral grid of colour transforms and its total-variation regulariser (csrc/bilagrid.hip).
 There is no CPU path and nothing here synchronises with the host."""
 from __future__ import annotations
 
@@ -314,3 +315,128 @@ def apply_exposure(img: torch.Tensor, M: torch.Tensor, channels_last: bool = Fal
     if torch.is_grad_enabled() and (img.requires_grad or M.requires_grad):
         return _ApplyExposure.apply(img, M, channels_last)
     return _launch_exposure(_as_vchw(img.detach(), channels_last), M.detach().reshape(-1, 3, 4).contiguous())
+
+
+# ---- per-view bilateral grid (csrc/bilagrid.hip) -----------------------------------------------------------------
+def _grid_dims(grids5: torch.Tensor) -> Tuple[int, int, int, int]:
+    V, _, L, Gh, Gw = grids5.shape
+    return int(V), int(L), int(Gh), int(Gw)
+
+
+def _launch_bilagrid(img4: torch.Tensor, grids5: torch.Tensor) -> torch.Tensor:
+    """One siu3r_bilagrid_apply call on a [V,3,H,W] view with arbitrary non-negative strides -> contiguous [V,3,H,W]"""
+    V, _, H, W = img4.shape
+    _, L, Gh, Gw = _grid_dims(grids5)
+    out = torch.empty((V, 3, H, W), dtype=torch.float32, device=img4.device)
+    with torch.cuda.device(img4.device):
+        check(_lib.lib().siu3r_bilagrid_apply(_p(img4), (C.c_int64 * 4)(*img4.stride()), _p(grids5), V, H, W, L, Gh, Gw, _p(out), _stream()))
+    return out
+
+
+class _ApplyBilagrid(torch.autograd.Function):
+    """The slice and its two backward kernels: the backward computes the gradients that are asked for, g_img in the image's stored layout."""
+
+    @staticmethod
+    def forward(ctx, img, grids, channels_last):
+        i4 = _expressible(_as_vchw(img.detach(), channels_last), img.requires_grad)
+        g5 = grids.detach().reshape(-1, *grids.shape[-4:]).contiguous()
+        ctx.save_for_backward(i4, g5)
+        ctx.channels_last, ctx.img_shape, ctx.grids_shape = channels_last, img.shape, grids.shape
+        return _launch_bilagrid(i4, g5)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_out):
+        i4, g5 = ctx.saved_tensors
+        want_img, want_grids = ctx.needs_input_grad[0], ctx.needs_input_grad[1]
+        if not (want_img or want_grids):
+            return None, None, None
+        V, _, H, W = i4.shape
+        _, L, Gh, Gw = _grid_dims(g5)
+        dev = i4.device
+        g_out = g_out.contiguous()
+        g_img = torch.empty_strided(tuple(i4.shape), tuple(i4.stride()), dtype=torch.float32, device=dev) if want_img else None
+        g_grids = torch.empty_like(g5) if want_grids else None
+        with torch.cuda.device(dev):
+            check(_lib.lib().siu3r_bilagrid_apply_bwd(_p(i4), (C.c_int64 * 4)(*i4.stride()), _p(g5), _p(g_out), V, H, W, L, Gh, Gw, _p(g_img), _p(g_grids),
+                                                      _stream()))
+        if want_img:
+            g_img = (g_img.permute(0, 2, 3, 1) if ctx.channels_last else g_img).reshape(ctx.img_shape)
+        return g_img, g_grids.reshape(ctx.grids_shape) if want_grids else None, None
+
+
+def _check_grids(grids: torch.Tensor, who: str):
+    if not isinstance(grids, torch.Tensor):
+        raise TypeError(f"grids must be a tensor, got {type(grids).__name__}")
+    _gpu(grids)
+    if grids.dtype != torch.float32:
+        raise ValueError(f"{who} takes float32 grids, got {grids.dtype}")
+    if grids.dim() not in (4, 5) or grids.numel() == 0 or grids.shape[-4] != 12 or min(grids.shape[-3:]) < 2 or grids.shape[-3] > 16:
+        raise ValueError(f"grids must be [V,12,L,Gh,Gw] (or [12,L,Gh,Gw]) with 2 <= L <= 16 and Gh, Gw >= 2, got {tuple(grids.shape)}")
+
+
+def apply_bilagrid(img: torch.Tensor, grids: torch.Tensor, channels_last: bool = False) -> torch.Tensor:
+    """Per-view bilateral grid of affine colour transforms (Wang et al. 2024; the `use_bilateral_grid` option of 3DGS trainers) applied to
+    float32 GPU images with 3 channels: img [V,3,H,W] (channels_last: [V,H,W,3]; a single image may drop V), read as stored; grids
+    [V,12,L,Gh,Gw] ([12,L,Gh,Gw] for a single image), channel 4c + k = entry (c, k) of a 3 x 4 matrix.  Each pixel's matrix is the trilinear
+    interpolation of the grid at ((x + 0.5) / W * (Gw - 1), (y + 0.5) / H * (Gh - 1), clamp(luminance, 0, 1) * (L - 1)), luminance =
+    0.299 r + 0.587 g + 0.114 b of the pixel itself (torch's grid_sample with align_corners=True and border padding).  Returns a contiguous
+    [V,3,H,W] tensor, as apply_exposure does.  Differentiable w.r.t. `img` (through the matrix and through the luminance; a clamped
+    luminance passes no guidance gradient; the gradient comes back in img's stored layout) and w.r.t. `grids` (deterministic gather); only
+    the gradients that are needed are computed.  An identity grid returns the bits of the input.  There is no CPU path and nothing here
+    synchronises with the host."""
+    if not isinstance(img, torch.Tensor):
+        raise TypeError(f"img must be a tensor, got {type(img).__name__}")
+    _check_grids(grids, "apply_bilagrid")
+    _gpu(img)
+    if img.dtype != torch.float32:
+        raise ValueError(f"apply_bilagrid takes a float32 image, got {img.dtype}")
+    if img.dim() not in (3, 4) or img.numel() == 0 or img.shape[-1 if channels_last else -3] != 3:
+        raise ValueError(f"img must be [V,3,H,W], [V,H,W,3] with channels_last, or one such image without V, got {tuple(img.shape)}")
+    V = 1 if img.dim() == 3 else img.shape[0]
+    if not (grids.dim() == 5 and grids.shape[0] == V) and not (img.dim() == 3 and grids.dim() == 4):
+        raise ValueError(f"grids must be [{V}, 12, L, Gh, Gw] for an image batch {tuple(img.shape)}, got {tuple(grids.shape)}")
+    if grids.device != img.device:
+        raise ValueError(f"img is on {img.device}, grids on {grids.device}")
+    if torch.is_grad_enabled() and (img.requires_grad or grids.requires_grad):
+        return _ApplyBilagrid.apply(img, grids, channels_last)
+    return _launch_bilagrid(_as_vchw(img.detach(), channels_last), grids.detach().reshape(-1, *grids.shape[-4:]).contiguous())
+
+
+def _launch_tv(grids5: torch.Tensor, want_grad: bool):
+    """One siu3r_bilagrid_tv call -> (value [1], d tv / d grids or None)"""
+    lib = _lib.lib()
+    V, L, Gh, Gw = _grid_dims(grids5)
+    dev = grids5.device
+    ws = torch.empty(int(lib.siu3r_bilagrid_tv_ws(V, L, Gh, Gw)) // 8, dtype=torch.float64, device=dev)
+    value = torch.empty(1, dtype=torch.float32, device=dev)
+    grad = torch.zeros_like(grids5) if want_grad else None
+    with torch.cuda.device(dev):
+        check(lib.siu3r_bilagrid_tv(_p(grids5), V, L, Gh, Gw, 1.0, _p(grad), _p(ws), _p(value), _stream()))
+    return value, grad
+
+
+class _BilagridTV(torch.autograd.Function):
+    """The forward call already produces d tv / d grids, the backward is one multiply."""
+
+    @staticmethod
+    def forward(ctx, grids):
+        value, grad = _launch_tv(grids.detach().reshape(-1, *grids.shape[-4:]).contiguous(), True)
+        ctx.save_for_backward(grad)
+        ctx.shape = grids.shape
+        return value[0]
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_value):
+        (grad,) = ctx.saved_tensors
+        return (grad * g_value).reshape(ctx.shape)
+
+
+def bilagrid_tv(grids: torch.Tensor) -> torch.Tensor:
+    """Total variation of bilateral grids [V,12,L,Gh,Gw] (or one [12,L,Gh,Gw]) as a 0-d device tensor: the mean over views of the sum over
+    the z, y and x axes of the mean squared forward difference along that axis.  Differentiable w.r.t. `grids`; deterministic."""
+    _check_grids(grids, "bilagrid_tv")
+    if torch.is_grad_enabled() and grids.requires_grad:
+        return _BilagridTV.apply(grids)
+    return _launch_tv(grids.detach().reshape(-1, *grids.shape[-4:]).contiguous(), False)[0][0]

@@ -12,10 +12,10 @@ from typing import Dict, List, Optional, Sequence, Tuple, Union
 import torch
 
 from . import raster
-from .cameras import CameraControl, CameraState
+from .cameras import CameraControl, CameraState, exposure_mode, identity_grids
 from .cuda_splatting import render_cuda
 from .density import FIELDS, DensityControl, DensityStats, densify_and_prune, scene_extent
-from .losses import DEPTH_MODES, DEPTH_SPACES, apply_exposure, depth_loss, photometric_loss
+from .losses import DEPTH_MODES, DEPTH_SPACES, apply_bilagrid, apply_exposure, bilagrid_tv, depth_loss, photometric_loss
 from .mcmc import MCMCControl, event as mcmc_event, inject_noise, regularize
 from .optim import GaussianAdam, TorchAdam, log_linear, means_lr_schedule
 
@@ -191,7 +191,14 @@ def refine_gaussians(means, scales, rotations, opacities, harmonics, images, c2w
     extent is still taken from the starting cameras.  params=() with a control is multi-view pose / exposure alignment against frozen
     Gaussians (without a control params=() runs no iteration).  The returned dict gains "c2w" [V,4,4], "exposure" [V,3,4] (identity where
     it is not optimised) and "camera_steps".  A control that moves nothing, a fixed index out of range, every view fixed and a
-    non-positive rate raise ValueError before any device work."""
+    non-positive rate raise ValueError before any device work.
+
+    control.exposure = "bilagrid" (True and "affine" are the transform above) replaces the one matrix per view by a bilateral grid of them
+    (control.bilagrid_shape = (Gh, Gw, L); csrc/bilagrid.hip): from control.start on the render goes through losses.apply_bilagrid, the
+    objective gains control.lambda_tv * losses.bilagrid_tv(grids), which `losses` logs with the rest, and after the Gaussians' optimiser step
+    the grids take an Adam step of their own (optim.GaussianAdam, rate control.lr_bilagrid decayed like the others; fixed views keep the
+    bits of the identity grid) before the camera launch steps the poses.  The returned dict gains "bilagrid" [V,12,L,Gh,Gw]; "exposure"
+    stays the identity.  An unknown exposure string raises ValueError before any device work."""
     lambdas_depth = _check_depth_args(images, depths, depth_weights, lambda_depth, depth_mode, depth_space, depth_min_opacity, iters)
     hip = _check_optim_args(optimizer, sparse, means_lr_final, means_lr_extent_scale, sh_rest_lr_scale)
     params = tuple(params)
@@ -292,9 +299,11 @@ def refine_gaussians(means, scales, rotations, opacities, harmonics, images, c2w
         cov6_fixed = None if cov_moves else cov6_of()
 
     cam = cam_rates = None  # the cameras' state and their (lr_trans, lr_rot, lr_exposure) per iteration from cameras.start on
+    grid_on = cameras is not None and exposure_mode(cameras.exposure) == "bilagrid"
     if cameras is not None and int(iters) > 0:
-        cam = CameraState(c2w, cameras.pose, cameras.exposure, cameras.fixed)
+        cam = CameraState(c2w, cameras.pose, cameras.exposure, cameras.fixed, bilagrid_shape=cameras.bilagrid_shape)
         cam_rates = cameras.rates(int(iters))
+        grid_rates = cameras.bilagrid_rates(int(iters)) if grid_on else None
     for it in range(int(iters) if free or cam is not None else 0):
         cam_on = cam is not None and it >= int(cameras.start)
         if not (free or cam_on):
@@ -319,6 +328,8 @@ def refine_gaussians(means, scales, rotations, opacities, harmonics, images, c2w
         img, dep = rendered[0], rendered[1]
         if cam_on and cam.exposure:
             img = apply_exposure(img, cam.M)
+        elif cam_on and grid_on:
+            img = apply_bilagrid(img, cam.grids)
         opa = _aux_cat(rendered[2], "opacity") if lambdas_depth is not None else None
         radii = _aux_cat(rendered[2], "radii") if sparse else None
         if lambdas_depth is None:
@@ -326,6 +337,8 @@ def refine_gaussians(means, scales, rotations, opacities, harmonics, images, c2w
         else:
             d_loss = depth_loss(dep, opa, depth_target, depth_conf, depth_mode, depth_space, depth_min_opacity)
             loss = photometric_loss(img, target, lambda_dssim) + lambdas_depth[it] * d_loss
+        if cam_on and grid_on and float(cameras.lambda_tv) > 0.0:
+            loss = loss + float(cameras.lambda_tv) * bilagrid_tv(cam.grids)
         loss.backward()
         if strategy.reg_o > 0.0 or strategy.reg_s > 0.0:
             reg = regularize(unc("opacities"), unc("scales"), strategy.reg_o, strategy.reg_s, free["opacities"].grad if strategy.reg_o > 0.0 else None,
@@ -334,7 +347,7 @@ def refine_gaussians(means, scales, rotations, opacities, harmonics, images, c2w
         if opt is not None:
             opt.step(visible=radii, lrs=None if means_lrs is None else {"means": means_lrs[it]})
         if cam_on:
-            cam.step(cam.step_count + 1, cam_rates[it - int(cameras.start)])
+            cam.step(cam.step_count + 1, cam_rates[it - int(cameras.start)], grid_rates[it - int(cameras.start)] if grid_on else None)
         if strategy.noise_lr > 0.0:
             scaler = strategy.noise_lr * (lr["means"] if means_lrs is None else means_lrs[it])
             noise = torch.randn((free["means"].shape[0], 3), generator=noise_gen, device=dev, dtype=torch.float32)
@@ -356,4 +369,6 @@ def refine_gaussians(means, scales, rotations, opacities, harmonics, images, c2w
             out["c2w"] = cam.c2w.clone() if cam is not None else c2w.clone()
             out["exposure"] = cam.M.detach().clone() if cam is not None else torch.eye(3, 4, device=dev).repeat(V, 1, 1)
             out["camera_steps"] = cam.step_count if cam is not None else 0
+            if grid_on:
+                out["bilagrid"] = cam.grids.detach().clone() if cam is not None else identity_grids(V, cameras.bilagrid_shape, dev)
     return out, losses
