@@ -444,6 +444,17 @@ int siu3r_raster_tune(int key, int value);
 int siu3r_raster_composite_rgb_bwd(const siu3r_raster_cam* cams_host, int V, const void* cams_dev, int64_t G, const int32_t* bin_start,
                                    const void* entries, int64_t cap_e, const float* rec, const float* image, const float* depth, const float* alpha,
                                    const float* g_image, const float* g_depth, const float* g_alpha, float* grad, void* stream);
+/* the same launch with the absolute-gradient densification statistics of AbsGS (Ye et al. 2024; an addition, ABI version unchanged):
+ * grad exactly as above, and abs_mean2d [V, G, 2] fp32 (zeroed here) = the sum over the pixels that blend the Gaussian of |that pixel's
+ * mean2d x term| and |its mean2d y term| -- the absolute value is taken per pixel, before any sum, so contributions of opposite sign
+ * from the two sides of a footprint do not cancel (|grad[.., 0..1]| <= abs_mean2d).  A pixel whose alpha sits on the alpha_max clamp
+ * contributes 0, as to grad; rows of Gaussians that blend nowhere stay exactly 0.  Float atomics, one per (tile, Gaussian, non-zero
+ * term).  Mode 0 cameras only (a mode-1 view array is refused); a null abs_mean2d is refused like a null grad (G == 0 writes nothing
+ * and accepts both). */
+int siu3r_raster_composite_rgb_bwd_abs(const siu3r_raster_cam* cams_host, int V, const void* cams_dev, int64_t G, const int32_t* bin_start,
+                                       const void* entries, int64_t cap_e, const float* rec, const float* image, const float* depth,
+                                       const float* alpha, const float* g_image, const float* g_depth, const float* g_alpha, float* grad,
+                                       float* abs_mean2d, void* stream);
 /* projection: grad [V, G, 10] -> g_means [G,3], g_cov [G, cov_stride] (stride 9: entries 0, 1, 2, 4, 5, 8, zeros elsewhere), g_opacities
  * [G], g_colors (the layout and size of colors; sh_degree < 0: the precomputed [G,1,3] colours), summed over the views (no atomics);
  * g_mean2d [V, G, 2] optional (pixel-space mean gradient); pose_part optional: [siu3r_raster_pose_partial_rows(G), V, 6] per-workgroup

@@ -9,7 +9,9 @@
 //                   BEHIND an entry (suffix) is the forward's saved total minus the running prefix.  Per entry, each wave sums its 64
 //                   pixels' ten gradient terms by cross-lane reduction (skipping terms that are zero on the whole wave) and adds them into
 //                   an LDS slot of the staged entry; after the slice the workgroup adds every non-zero slot to global memory: one float atomic per
-//                   (tile, Gaussian, term).
+//                   (tile, Gaussian, term).  ABS (compile time, K2 only): the same walk also sums |mean x term| and |mean y term| per
+//                   pixel (AbsGS, Ye et al. 2024: the densification signal that does not cancel over a Gaussian's footprint) through two
+//                   more slots of the staged entry into abs_mean2d [V,G,2]; the signed record is formed exactly as without it.
 //   projection bwd  one thread per Gaussian, looping over the call's views like project_kernel: per-Gaussian gradients are plain stores.
 //                   The six pose terms of a view are summed per workgroup into a partial row; rows_reduce_kernel<6, 6> sums the rows.
 // The gradient is that of the function the forward computes, on the branch it took: culling, tile rects, the alpha_min cut-off,
@@ -27,18 +29,21 @@ typedef siu3r_raster_cam Cam;
 constexpr int BSTG = 256;  // entries staged per slice
 // K3 (compile time): the gsplat family's conventions on the same walk, as composite_rgb_kernel<NT, K3> -- pixel centres at +0.5, saturation
 // test nT <= t_min, channel-last [V,H,W,3] colours and their gradient, no depth (depth / g_depth unused), no background (blended outside).
-template <bool K3 = false>
+// ABS (compile time): two more slots per staged entry, the wave sums of |gv[GR_MX]| and |gv[GR_MY]|, flushed into abs_mean2d [V,G,2].  Every
+// addition is under `if constexpr`: the plain instantiations keep their registers, their LDS (row stride GR_N) and their code.
+template <bool K3 = false, bool ABS = false>
 __global__ __launch_bounds__(256) void composite_rgb_bwd_kernel(const Cam* __restrict__ cams, Geo geo, const int32_t* __restrict__ bin_start,
                                                                 const uint2* __restrict__ entries, int64_t cap_e, const float* __restrict__ rec, int64_t G,
                                                                 const float* __restrict__ image, const float* __restrict__ depth,
                                                                 const float* __restrict__ alpha, const float* __restrict__ g_image,
                                                                 const float* __restrict__ g_depth, const float* __restrict__ g_alpha,
-                                                                float* __restrict__ grad) {
+                                                                float* __restrict__ grad, float* __restrict__ abs_mean2d) {
+  constexpr int GS = ABS ? GR_N + 2 : GR_N;                     // slots per staged entry
   __shared__ __attribute__((aligned(16))) float s_a[BSTG][4];   // mx, my, depth, id
   __shared__ __attribute__((aligned(16))) float s_co[BSTG][4];  // conic a, b, c, opacity
   __shared__ __attribute__((aligned(16))) float s_c[BSTG][4];   // r, g, b
   __shared__ int s_m[BSTG];                                     // quadrant mask (the forward's)
-  __shared__ float s_g[BSTG][GR_N];                             // the tile's summed gradient terms per staged entry
+  __shared__ float s_g[BSTG][GS];                               // the tile's summed gradient terms per staged entry (ABS: + |mx|, |my|)
   __shared__ int s_wcnt[4];
   const int v = blockIdx.y;
   const Cam& c = cams[v];
@@ -113,7 +118,7 @@ __global__ __launch_bounds__(256) void composite_rgb_bwd_kernel(const Cam* __res
       *(float4*)s_c[off] = r2;
       s_m[off] = quadrant_mask<K3>(r0, r1, alpha_min, tile_x0, tile_y0);  // the forward's: a wave skips exactly the entries the forward's wave skipped
 #pragma unroll
-      for (int k = 0; k < GR_N; ++k) s_g[off][k] = 0.f;
+      for (int k = 0; k < GS; ++k) s_g[off][k] = 0.f;
     }
     base += 256;
     __syncthreads();
@@ -167,16 +172,32 @@ __global__ __launch_bounds__(256) void composite_rgb_bwd_kernel(const Cam* __res
             const float s = wave_sum(gv[k]);
             if (lane == 0 && s != 0.f) atomicAdd(&s_g[j][k], s);  // (up to four waves per slot)
           }
+          if constexpr (ABS) {
+            // the pixel's |mean terms|: 0 where it does not blend and where its alpha sits on the clamp, as the signed terms are
+#pragma unroll
+            for (int k = 0; k < 2; ++k) {
+              const float av = fabsf(gv[k == 0 ? GR_MX : GR_MY]);
+              if (__ballot(av != 0.f) == 0ull) continue;
+              const float s = wave_sum(av);
+              if (lane == 0 && s != 0.f) atomicAdd(&s_g[j][GR_N + k], s);
+            }
+          }
         }
         if (__ballot(!done) == 0ull) break;
       }
     }
     __syncthreads();
     // one global add per (tile, Gaussian, non-zero term): ten consecutive lanes cover one Gaussian's 40-byte row
-    for (int q = t; q < n * GR_N; q += 256) {
-      const int j = q / GR_N, k = q - j * GR_N;
+    // (ABS: twelve lanes per Gaussian, the last two add into its 8-byte row of abs_mean2d)
+    for (int q = t; q < n * GS; q += 256) {
+      const int j = q / GS, k = q - j * GS;
       const float s = s_g[j][k];
-      if (s != 0.f) atomicAdd(&grad[(vg + __float_as_int(s_a[j][3])) * GR_N + k], s);
+      if constexpr (ABS) {
+        const int64_t row = vg + __float_as_int(s_a[j][3]);
+        if (s != 0.f) atomicAdd(k < GR_N ? &grad[row * GR_N + k] : &abs_mean2d[row * 2 + (k - GR_N)], s);
+      } else {
+        if (s != 0.f) atomicAdd(&grad[(vg + __float_as_int(s_a[j][3])) * GR_N + k], s);
+      }
     }
   }
 }
@@ -323,24 +344,26 @@ __global__ __launch_bounds__(256) void project_bwd_kernel(const Cam* __restrict_
   }
 }
 
-// the launcher body of both composite backwards (K3: no depth)
-template <bool K3>
+// the launcher body of the composite backwards (K3: no depth; ABS: + abs_mean2d [V,G,2], zeroed here like grad)
+template <bool K3, bool ABS = false>
 int composite_rgb_bwd(const char* who, const siu3r_raster_cam* cams_host, int V, const void* cams_dev, int64_t G, const int32_t* bin_start, const void* entries,
                       int64_t cap_e, const float* rec, const float* image, const float* depth, const float* alpha, const float* g_image, const float* g_depth,
-                      const float* g_alpha, float* grad, void* stream) {
+                      const float* g_alpha, float* grad, float* abs_mean2d, void* stream) {
   if (int rc = check_views(cams_host, V, K3 ? 1 : 0, who)) return rc;
-  SIU3R_CHECK(cams_dev && bin_start && image && alpha && g_image && g_alpha && (K3 || (depth && g_depth)) && (G == 0 || (entries && rec && grad)),
+  SIU3R_CHECK(cams_dev && bin_start && image && alpha && g_image && g_alpha && (K3 || (depth && g_depth)) &&
+                  (G == 0 || (entries && rec && grad && (!ABS || abs_mean2d))),
               "%s: null pointer", who);
   SIU3R_CHECK(G >= 0 && G < (1ll << 31) && cap_e > 0, "%s: bad sizes", who);
   hipStream_t s = (hipStream_t)stream;
   if (G == 0) return 0;
-  if (hipMemsetAsync(grad, 0, sizeof(float) * GR_N * (size_t)V * G, s) != hipSuccess) {
+  if (hipMemsetAsync(grad, 0, sizeof(float) * GR_N * (size_t)V * G, s) != hipSuccess ||
+      (ABS && hipMemsetAsync(abs_mean2d, 0, sizeof(float) * 2 * (size_t)V * G, s) != hipSuccess)) {
     siu3r_set_error("%s: memset failed", who);
     return 2;
   }
   const Geo geo = make_geo(cams_host[0].width, cams_host[0].height);
-  hipLaunchKernelGGL(composite_rgb_bwd_kernel<K3>, dim3(geo.T, V), dim3(256), 0, s, (const Cam*)cams_dev, geo, bin_start, (const uint2*)entries, cap_e, rec, G,
-                     image, depth, alpha, g_image, g_depth, g_alpha, grad);
+  hipLaunchKernelGGL((composite_rgb_bwd_kernel<K3, ABS>), dim3(geo.T, V), dim3(256), 0, s, (const Cam*)cams_dev, geo, bin_start, (const uint2*)entries, cap_e,
+                     rec, G, image, depth, alpha, g_image, g_depth, g_alpha, grad, abs_mean2d);
   SIU3R_LAUNCH_CHECK(who);
   return 0;
 }
@@ -352,14 +375,22 @@ extern "C" int siu3r_raster_composite_rgb_bwd(const siu3r_raster_cam* cams_host,
                                               const float* alpha, const float* g_image, const float* g_depth, const float* g_alpha, float* grad,
                                               void* stream) {
   return composite_rgb_bwd<false>("siu3r_raster_composite_rgb_bwd", cams_host, V, cams_dev, G, bin_start, entries, cap_e, rec, image, depth, alpha, g_image, g_depth,
-                                  g_alpha, grad, stream);
+                                  g_alpha, grad, nullptr, stream);
+}
+
+extern "C" int siu3r_raster_composite_rgb_bwd_abs(const siu3r_raster_cam* cams_host, int V, const void* cams_dev, int64_t G, const int32_t* bin_start,
+                                                  const void* entries, int64_t cap_e, const float* rec, const float* image, const float* depth,
+                                                  const float* alpha, const float* g_image, const float* g_depth, const float* g_alpha, float* grad,
+                                                  float* abs_mean2d, void* stream) {
+  return composite_rgb_bwd<false, true>("siu3r_raster_composite_rgb_bwd_abs", cams_host, V, cams_dev, G, bin_start, entries, cap_e, rec, image, depth, alpha,
+                                        g_image, g_depth, g_alpha, grad, abs_mean2d, stream);
 }
 
 extern "C" int siu3r_raster_composite_rgb_bwd_k3(const siu3r_raster_cam* cams_host, int V, const void* cams_dev, int64_t G, const int32_t* bin_start,
                                                  const void* entries, int64_t cap_e, const float* rec, const float* colors, const float* alphas,
                                                  const float* g_colors, const float* g_alphas, float* grad, void* stream) {
   return composite_rgb_bwd<true>("siu3r_raster_composite_rgb_bwd_k3", cams_host, V, cams_dev, G, bin_start, entries, cap_e, rec, colors, nullptr, alphas, g_colors,
-                                 nullptr, g_alphas, grad, stream);
+                                 nullptr, g_alphas, grad, nullptr, stream);
 }
 
 extern "C" int siu3r_raster_project_bwd(const siu3r_raster_cam* cams_host, int V, const void* cams_dev, int64_t G, const float* means, const float* cov,

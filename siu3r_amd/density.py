@@ -29,10 +29,14 @@ def _f32(x: float) -> float:
 class DensityStats:
     """The running statistics of G Gaussians between two density events: grad_accum [G] f32 (sum over the views that saw the Gaussian of
     the norm of its NDC-space mean gradient), seen [G] i32 (how many views did), max_radius [G] i32 (largest screen radius, pixels).
-    Hand it to cuda_splatting.render_cuda / raster.rasterize_views_k2 as `density_stats`: the backward of that render accumulates into it."""
+    Hand it to cuda_splatting.render_cuda / raster.rasterize_views_k2 as `density_stats`: the backward of that render accumulates into it.
+    absgrad=True asks that backward for the absolute-gradient statistics of AbsGS (Ye et al. 2024): per view, the sums over the pixels of
+    |the pixel's mean x term| and |its mean y term| (siu3r_raster_composite_rgb_bwd_abs) take the place of the signed mean gradient, so
+    pulls of opposite sign on the two sides of a footprint add up where the signed sum cancels them.  `accumulate` is the same either way."""
 
-    def __init__(self, G: int, device):
+    def __init__(self, G: int, device, absgrad: bool = False):
         self.G = int(G)
+        self.absgrad = bool(absgrad)
         self.grad_accum = torch.zeros(self.G, dtype=torch.float32, device=device)
         self.seen = torch.zeros(self.G, dtype=torch.int32, device=device)
         self.max_radius = torch.zeros(self.G, dtype=torch.int32, device=device)
@@ -79,7 +83,11 @@ class DensityControl:
     An event at iteration i runs BEFORE the render of iteration i, on the statistics of the iterations since the last event.
     stop = None means iters - every: no event so late that the new Gaussians get no steps.  reset_every > 0 resets the opacities to at
     most reset_opacity every that many iterations, up to `stop`.  max_gaussians caps growth: an event that would exceed it only prunes.
-    scene_extent = None takes 1.1 x the largest distance of a camera centre from the centres' mean (the 3DGS cameras_extent)."""
+    scene_extent = None takes 1.1 x the largest distance of a camera centre from the centres' mean (the 3DGS cameras_extent).
+    absgrad = True thresholds the absolute-gradient statistics (DensityStats(absgrad=True); AbsGS, Ye et al. 2024) in place of the signed
+    ones: a large Gaussian over fine detail, whose per-pixel pulls cancel in the signed sum, then reaches the threshold and is split.
+    The absolute sums are never smaller than the signed ones; gsplat pairs absgrad with a threshold of 8e-4.  grad_threshold is NOT
+    changed automatically: pass it."""
     grad_threshold: float = 2e-4
     percent_dense: float = 0.01
     min_opacity: float = 0.005
@@ -93,6 +101,7 @@ class DensityControl:
     max_gaussians: Optional[int] = None
     scene_extent: Optional[float] = None
     seed: int = 0
+    absgrad: bool = False
 
     def events(self, iters: int) -> Tuple[List[int], List[int]]:
         """(iterations that densify, iterations that reset the opacities) of a run of `iters` iterations: start, start + every, ... up to

@@ -405,7 +405,9 @@ def rasterize_views_k2(cams: Sequence[RasterCam], means, cov6, shs, opacities, w
     pixel-space mean gradient summed over the views (the caller scales it).  Every other call runs the plain forward.
     density_stats: a density.DensityStats of G Gaussians; the backward of a differentiable call accumulates the per-view NDC-space mean
     gradient norms (scaled by V: DensityStats.accumulate), the visibility counts and the largest radii into it.  The forward does not
-    look at it, and None (the default) leaves the backward exactly as it is without the keyword."""
+    look at it, and None (the default) leaves the backward exactly as it is without the keyword.  With density_stats.absgrad the composite
+    backward is siu3r_raster_composite_rgb_bwd_abs and the norms are those of its abs_mean2d (AbsGS); every returned gradient, means2d's
+    included, stays the signed one."""
     wants_grad = _wants_grad(means, cov6, shs, opacities, pose_delta, means2d)
     if wants_grad:
         _no_deferred(check_overflow)
@@ -441,13 +443,19 @@ class _RasterizeK2(torch.autograd.Function):
         lib = _lib.lib()
         V, G, dev = st.V, st.G, image.device
         ncoef = shs_c.shape[2] if ctx.sh_planar else shs_c.shape[1]
-        check(lib.siu3r_raster_composite_rgb_bwd(st.cams, V, _p(st.cams_dev), G, _p(st.bin_start), _p(st.entries), st.cap_e, _p(st.rec),
-                                                 _p(image), _p(depth), _p(opacity), _p(g_image), _p(g_depth), _p(g_opacity), _p(grad), _stream()))
-        need_pose, need_m2d = ctx.needs_input_grad[7], ctx.needs_input_grad[8]
         stats = ctx.density_stats
+        composite = (st.cams, V, _p(st.cams_dev), G, _p(st.bin_start), _p(st.entries), st.cap_e, _p(st.rec), _p(image), _p(depth), _p(opacity), _p(g_image),
+                     _p(g_depth), _p(g_opacity), _p(grad))
+        abs_m2d = None  # absolute-gradient statistics: the per-pixel |mean terms|, summed by the same launch (the call zeroes them)
+        if stats is not None and stats.absgrad:
+            abs_m2d = torch.empty((V, G, 2), dtype=torch.float32, device=dev)
+            check(lib.siu3r_raster_composite_rgb_bwd_abs(*composite, _p(abs_m2d), _stream()))
+        else:
+            check(lib.siu3r_raster_composite_rgb_bwd(*composite, _stream()))
+        need_pose, need_m2d = ctx.needs_input_grad[7], ctx.needs_input_grad[8]
         g_means, g_cov, g_op, g_sh = torch.empty_like(means_c), torch.empty_like(cov_c), torch.empty_like(op_c), torch.empty_like(shs_c)
         g_m2d = torch.zeros((V, G, 2), dtype=torch.float32, device=dev) if need_m2d else None  # (culled Gaussians: not written)
-        if stats is not None and g_m2d is None:
+        if stats is not None and abs_m2d is None and g_m2d is None:
             g_m2d = torch.empty((V, G, 2), dtype=torch.float32, device=dev)  # (the statistics go by the radii, never by an unwritten row)
         rows = int(lib.siu3r_raster_pose_partial_rows(G))
         part = torch.empty((max(rows, 1), V, 6), dtype=torch.float32, device=dev) if need_pose else None
@@ -455,7 +463,7 @@ class _RasterizeK2(torch.autograd.Function):
                                            int(bool(ctx.sh_planar)), _p(st.rect), _p(grad), _p(g_means), _p(g_cov), _p(g_op), _p(g_sh), _p(g_m2d),
                                            _p(part), _stream()))
         if stats is not None:
-            stats.accumulate(g_m2d, st.radii, 0.5 * V * st.W, 0.5 * V * st.H)
+            stats.accumulate(g_m2d if abs_m2d is None else abs_m2d, st.radii, 0.5 * V * st.W, 0.5 * V * st.H)
         g_pose = None
         if need_pose:
             g_pose = torch.empty((V, 6), dtype=torch.float32, device=dev)

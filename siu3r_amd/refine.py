@@ -150,6 +150,8 @@ def refine_gaussians(means, scales, rotations, opacities, harmonics, images, c2w
     opacities to at most logit(control.reset_opacity) and zeroes their moments (frozen opacities could never recover and are left
     alone).  Every returned tensor then has the new row count, and the dict gains "density_events": one info dict per event
     (densify_and_prune's counts plus "iteration").  control.scene_extent = None costs one host read of the camera centres.
+    control.absgrad = True keeps the absolute-gradient statistics of AbsGS instead (DensityStats(absgrad=True), at the start and after
+    every event); the events, their info dicts and the threshold the control names are used as they are.
 
     density may instead be a mcmc.MCMCControl: the budgeted strategy of Kheradmand et al. 2024 (3DGS as Markov-chain Monte Carlo).  No
     statistics are kept (the render gets density_stats=None).  At the iterations control.events(iters) names, before that iteration's
@@ -252,7 +254,7 @@ def refine_gaussians(means, scales, rotations, opacities, harmonics, images, c2w
         noise_gen = torch.Generator(device=dev).manual_seed(int(density.seed))  # the events' split noise, or their random words and every iteration's noise
         if classic:
             density.thresholds(extent)  # (a bad extent raises here, not at the first event)
-            strategy = _Strategy(*density.events(int(iters)), stats=DensityStats(means.shape[0], dev))
+            strategy = _Strategy(*density.events(int(iters)), stats=DensityStats(means.shape[0], dev, absgrad=density.absgrad))
         else:  # (a frozen field's regulariser term is a constant: neither added nor logged; frozen means take no noise)
             strategy = _Strategy(density.events(int(iters)), reg_o=float(density.opacity_reg) if "opacities" in free else 0.0,
                                  reg_s=float(density.scale_reg) if "scales" in free else 0.0, noise_lr=float(density.noise_lr) if "means" in free else 0.0)
@@ -287,7 +289,7 @@ def refine_gaussians(means, scales, rotations, opacities, harmonics, images, c2w
             new_p, new_m, info = densify_and_prune(fields, opt.moments, strategy.stats, density, extent, noise)
             if info["rows_out"] == 0:
                 raise RuntimeError(f"density control pruned every Gaussian at iteration {it}: {info}")
-            strategy.stats = DensityStats(info["rows_out"], dev)
+            strategy.stats = DensityStats(info["rows_out"], dev, absgrad=density.absgrad)
         else:
             new_p, new_m, info = mcmc_event(fields, opt.moments, density, generator=noise_gen)
         events.append(dict(info, iteration=it))
