@@ -436,6 +436,18 @@ int siu3r_raster_composite_feat_ws(const siu3r_raster_cam* cams_host, int V, con
 /* tuning / A-B switches of the rasterizer (not for concurrent use).  key 0: 1 = the 32-channel kernel for every N-channel composite, 0 =
  * default (matrix-core form where it applies); key 1: accumulator blocks per chunk of the matrix-core form (1 .. 6, default 6) */
 int siu3r_raster_tune(int key, int value);
+/* per-Gaussian blend-contribution statistics (csrc/contrib.hip; an addition, ABI version unchanged).  Consumes the state of a forward
+ * call (project -> sort -> bin) exactly as siu3r_raster_composite_rgb does and re-walks it without colours, either family (mode 0: pixel
+ * centres at integers, saturation nT < t_min; mode 1: centres at +0.5, nT <= t_min; a mixed array is refused).  With w = alpha * T the very
+ * float the forward adds into a pixel, over the pixels of view v that blend Gaussian g (reached, not the saturating entry):
+ *   wmax  [V, G] fp32   the largest w (rows that blend nowhere stay exactly 0.0f)
+ *   count [V, G] int32  the number of those pixels                                              (optional: NULL = not wanted)
+ *   wsum  [V, G] uint64 the sum of (uint64_t)(w * 2^40): a fixed-point sum in units of 2^-40    (optional: NULL = not wanted)
+ * All three are zeroed here and reduced with integer operations only (the maximum on the bit patterns of w >= 0), so they are
+ * bit-reproducible.  A view whose coarse-bin entries overflowed (bin_start[v][NB] > cap_e) gets NaN in every element of its wmax row and
+ * zeros in count and wsum.  G == 0 writes nothing and accepts null pointers; a null wmax with G > 0 is refused. */
+int siu3r_raster_contrib(const siu3r_raster_cam* cams_host, int V, const void* cams_dev, int64_t G, const int32_t* bin_start, const void* entries,
+                         int64_t cap_e, const float* rec, float* wmax, int32_t* count, uint64_t* wsum, void* stream);
 /* ---- K2 backward (mode 0 cameras only; additions of ABI 10, backward compatible).  The forward's state of the same call is reused:
  * cams_dev, bin_start, entries, cap_e, rec, rect and the outputs image [V,3,H,W] (with background), depth [V,H,W], alpha [V,H,W].
  * composite: upstream gradients g_image / g_depth / g_alpha (shapes of the outputs) -> grad [V, G, 10] fp32 (zeroed here) =

@@ -156,6 +156,7 @@ SIGNATURES = {
     "siu3r_raster_project_c2w": [C.POINTER(RasterCam), _I, _P, _P, _P, _F, _L, _P, _P, _I, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P],
     "siu3r_raster_composite_rgb_bwd": [C.POINTER(RasterCam), _I, _P, _L, _P, _P, _L, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "siu3r_raster_composite_rgb_bwd_abs": [C.POINTER(RasterCam), _I, _P, _L, _P, _P, _L, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
+    "siu3r_raster_contrib": [C.POINTER(RasterCam), _I, _P, _L, _P, _P, _L, _P, _P, _P, _P, _P],
     "siu3r_raster_project_bwd": [C.POINTER(RasterCam), _I, _P, _L, _P, _P, _I, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "siu3r_raster_pose_partial_rows": [_L],
     "siu3r_raster_pose_reduce": [_I, _L, _P, _P, _P],

@@ -497,6 +497,48 @@ def rasterize_k2(cam: RasterCam, means, cov6, shs, opacities, **kw) -> Dict[str,
                 n_touched=None if o["n_touched"] is None else o["n_touched"][0], state=o["state"])
 
 
+def _contributions(cams, means, cov6, opacities, colors, channels, pose, entry_capacity, check_overflow, want_count, want_sum):
+    def composite(st, _chan):
+        wmax = _empty(st, st.V, st.G)
+        count = _empty(st, st.V, st.G, dtype=torch.int32) if want_count else None
+        wsum = _empty(st, st.V, st.G, dtype=torch.int64) if want_sum else None
+        check(_lib.lib().siu3r_raster_contrib(st.cams, st.V, _p(st.cams_dev), st.G, _p(st.bin_start), _p(st.entries), st.cap_e, _p(st.rec), _p(wmax),
+                                              _p(count), _p(wsum), _stream()))
+        return dict(wmax=wmax, count=count, wsum=wsum, radii=st.radii, state=st)
+
+    _gpu(means, cov6, opacities)
+    means, cov6, opacities = (t.detach() for t in (means, cov6, opacities))
+    return _render(cams, means, cov6, opacities, means if colors is None else colors, channels, pose, entry_capacity, check_overflow, composite)
+
+
+def contributions_k2(cams: Sequence[RasterCam], means, cov6, opacities, entry_capacity=None, check_overflow=True, pose_c2w=None, want_count=True,
+                     want_sum=True) -> Dict[str, torch.Tensor]:
+    """Blend-contribution statistics of V views of one Gaussian set, 3DGS family (siu3r_raster_contrib): with w = alpha * T the very float
+    rasterize_views_k2 adds into a pixel, over the pixels of view v that blend Gaussian g -> wmax [V,G] f32 (the largest w; exactly 0 where g
+    blends nowhere), count [V,G] i32 (the number of those pixels), wsum [V,G] i64 (the sum of trunc(w * 2^40): fixed point, units of 2^-40),
+    radii [V,G,2] i32 + the call's state.  Integer reductions only: two calls give the same bits.  entry_capacity / check_overflow /
+    pose_c2w as in rasterize_views_k2 (a view that overflowed an unchecked call has a NaN wmax row and zero count / wsum).  Colours take no
+    part: the call projects with sh_degree = -1 on its own copy of the camera blocks and hands the projection `means` as the [G,3] colour
+    operand it insists on -- no SH evaluation and no colour tensor.  No autograd: the inputs are detached.  want_count / want_sum = False
+    leave that output None."""
+    k2 = []
+    for c in cams:
+        c2 = RasterCam()
+        C.memmove(C.byref(c2), C.byref(c), C.sizeof(RasterCam))
+        c2.sh_degree, c2.sh_band4 = -1, 0
+        k2.append(c2)
+    return _contributions(k2, means, cov6, opacities, means.detach().contiguous().float(), 1, _pose(len(cams), means.device, pose_c2w=pose_c2w), entry_capacity,
+                          check_overflow, want_count, want_sum)
+
+
+def contributions_k3(cams: Sequence[RasterCam], means, cov6, opacities, entry_capacity=None, check_overflow=True, pose_dev=None, pose_c2w=None,
+                     want_count=True, want_sum=True) -> Dict[str, torch.Tensor]:
+    """contributions_k2 for the gsplat family (pixel centres at +0.5, saturation nT <= t_min): w is the weight rasterize_views_k3 and
+    rasterize_views_k3_rgb give the Gaussian's feature row in that pixel.  The mode-1 projection takes no colour operand at all."""
+    return _contributions(cams, means, cov6, opacities, None, 0, _pose(len(cams), means.device, pose_dev, pose_c2w), entry_capacity, check_overflow,
+                          want_count, want_sum)
+
+
 def tune(key: int, value: int) -> None:
     """siu3r_raster_tune: key 0 -- 1 = the 32-channel kernel for every N-channel composite (features that may be non-finite; A/B), 0 = default;
     key 1 -- accumulator blocks per chunk of the matrix-core composite (1 .. 6).  Process-wide, not for concurrent use."""

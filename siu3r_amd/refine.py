@@ -18,6 +18,7 @@ from .density import FIELDS, DensityControl, DensityStats, densify_and_prune, sc
 from .losses import DEPTH_MODES, DEPTH_SPACES, apply_bilagrid, apply_exposure, bilagrid_tv, depth_loss, photometric_loss
 from .mcmc import MCMCControl, event as mcmc_event, inject_noise, regularize
 from .optim import GaussianAdam, TorchAdam, log_linear, means_lr_schedule
+from .prune import ContributionPrune, gaussian_contributions, prune_by_contribution
 
 # Adam steps per field, those of the 3DGS training recipe (Kerbl et al. 2023): position 1.6e-4, scaling 5e-3, rotation 1e-3, opacity 5e-2,
 # SH 2.5e-3.  The recipe also multiplies the position rate by the scene extent and decays it, and steps the higher SH bands at a twentieth:
@@ -121,7 +122,8 @@ def refine_gaussians(means, scales, rotations, opacities, harmonics, images, c2w
                      density: Union[DensityControl, MCMCControl, None] = None, depths=None, depth_weights=None, lambda_depth=0.0, depth_mode: str = "l1",
                      depth_space: str = "depth", depth_min_opacity: float = 0.5, optimizer: str = "torch", sparse: bool = False,
                      means_lr_final: Optional[float] = None, means_lr_extent_scale: bool = False,
-                     sh_rest_lr_scale: float = 1.0, cameras: Optional[CameraControl] = None) -> Tuple[Dict[str, torch.Tensor], List[float]]:
+                     sh_rest_lr_scale: float = 1.0, cameras: Optional[CameraControl] = None,
+                     prune: Optional[ContributionPrune] = None) -> Tuple[Dict[str, torch.Tensor], List[float]]:
     """means [G,3], scales [G,3], rotations [G,4], opacities [G], harmonics [G,3,n] (n = (deg+1)^2): what `Gaussians` carries, on the GPU.
     images [V,3,H,W]: the posed target views; c2w [V,4,4] camera-to-world, Kn [V,3,3] (or [3,3]) normalised intrinsics, near / far floats
     (or [V]), bg 3 floats: render_cuda's conventions.
@@ -200,7 +202,19 @@ def refine_gaussians(means, scales, rotations, opacities, harmonics, images, c2w
     objective gains control.lambda_tv * losses.bilagrid_tv(grids), which `losses` logs with the rest, and after the Gaussians' optimiser step
     the grids take an Adam step of their own (optim.GaussianAdam, rate control.lr_bilagrid decayed like the others; fixed views keep the
     bits of the identity grid) before the camera launch steps the poses.  The returned dict gains "bilagrid" [V,12,L,Gh,Gw]; "exposure"
-    stays the identity.  An unknown exposure string raises ValueError before any device work."""
+    stays the identity.  An unknown exposure string raises ValueError before any device work.
+
+    prune: a prune.ContributionPrune removes the Gaussians that contribute to no training view; None, the default, is the loop above: nothing
+    is launched, allocated or read that is not without the keyword.  At the iterations prune.events(iters) names, before that iteration's
+    render and after a density event of the same iteration, prune.gaussian_contributions renders the blend statistics of ALL training views
+    with the current parameters and the current poses (the cameras' when a CameraControl moves them) and prune.prune_by_contribution drops
+    the rows whose largest blending weight stays below prune.min_weight (or that fewer than min_views views blend, or beyond the
+    keep_at_most largest weight sums), over all five fields, free or frozen, and the free ones' Adam moments; kept rows keep their bits and
+    their order, the optimiser moves to the new leaves with its step count, and a classic control's statistics start over at the new size.
+    One host read per event.  prune.final = True runs one more event after the last iteration, so the returned set is pruned.  The returned
+    dict gains "prune_events": one info dict per event (prune_by_contribution's counts plus "iteration"; the final one carries `iters`).
+    An event that would leave no Gaussian raises RuntimeError.  An MCMCControl keeps an exact row count and relocates its dead rows itself:
+    prune= together with it, and a schedule with every <= 0, raise ValueError before any device work."""
     lambdas_depth = _check_depth_args(images, depths, depth_weights, lambda_depth, depth_mode, depth_space, depth_min_opacity, iters)
     hip = _check_optim_args(optimizer, sparse, means_lr_final, means_lr_extent_scale, sh_rest_lr_scale)
     params = tuple(params)
@@ -217,6 +231,9 @@ def refine_gaussians(means, scales, rotations, opacities, harmonics, images, c2w
     budgeted = isinstance(density, MCMCControl)  # which of the two strategies a control is: said here, read where they differ
     if budgeted:
         density.validate(means.shape[0])
+    if prune is not None and budgeted:
+        raise ValueError("prune= cannot be combined with an MCMCControl: the budgeted strategy keeps an exact row count and relocates its dead rows itself")
+    prune_at = () if prune is None else tuple(prune.events(int(iters)))
     if int(iters) <= 0:
         params = ()
     dev = means.device
@@ -245,6 +262,7 @@ def refine_gaussians(means, scales, rotations, opacities, harmonics, images, c2w
     losses: List[float] = []
     depth_losses: List[float] = []
     events: List[dict] = []
+    prune_events: List[dict] = []
     classic = density is not None and not budgeted
     extent = None  # of the scene: one host read unless the control names it
     if (classic and free) or (means_lr_extent_scale and "means" in free):
@@ -282,7 +300,7 @@ def refine_gaussians(means, scales, rotations, opacities, harmonics, images, c2w
         """one density event before iteration `it`'s render: all five fields in unconstrained form and the free ones' moments go through the
         strategy's one function (clone / split / prune, or relocate in place and grow); where it hands back new tensors they become the
         leaves and the optimiser moves to them (its step count stays); the frozen fields, cov6_fixed and the classic statistics follow"""
-        nonlocal free, cov6_fixed
+        nonlocal cov6_fixed
         fields = {k: unc(k) for k in FIELDS}
         if classic:
             noise = torch.randn((strategy.stats.G, 2, 3), generator=noise_gen, device=dev, dtype=torch.float32)
@@ -294,11 +312,35 @@ def refine_gaussians(means, scales, rotations, opacities, harmonics, images, c2w
             new_p, new_m, info = mcmc_event(fields, opt.moments, density, generator=noise_gen)
         events.append(dict(info, iteration=it))
         if new_p is not fields:  # (MCMC with nothing to add keeps its leaves)
-            free = {k: new_p[k].requires_grad_(True) for k in free}
-            opt.rebind(free, new_m)
+            adopt(new_p, new_m)
         frozen.update({k: new_p[k] for k in FIELDS if k not in free})
         start.update({k: _FROM_PARAM[k](v) for k, v in frozen.items()})
         cov6_fixed = None if cov_moves else cov6_of()
+
+    def adopt(new_p, new_m):
+        """the new tensors of an event become the leaves and the optimiser moves to them (its step count stays)"""
+        nonlocal free
+        free = {k: new_p[k].requires_grad_(True) for k in free}
+        opt.rebind(free, new_m)
+
+    def prune_event(it: int):
+        """one contribution-pruning event before iteration `it`'s render (after the last one: it == iters): the statistics of all training
+        views under the current poses, then the row selection over all five fields and the free ones' moments, then event()'s hand-over"""
+        nonlocal cov6_fixed
+        stats = gaussian_contributions(value("means"), value("scales"), value("rotations"), value("opacities"), c2w if cam is None else cam.c2w, Kn, near_t,
+                                       far_t, (H, W))
+        fields = {k: unc(k) for k in FIELDS}
+        new_p, new_m, info = prune_by_contribution(fields, stats, prune.min_weight, prune.min_views, prune.keep_at_most, opt.moments if free else None)
+        if info["rows_out"] == 0:
+            raise RuntimeError(f"contribution pruning removed every Gaussian at iteration {it}: {info}")
+        prune_events.append(dict(info, iteration=it))
+        if free:
+            adopt(new_p, new_m)
+        frozen.update({k: new_p[k] for k in FIELDS if k not in free})
+        start.update({k: _FROM_PARAM[k](v) for k, v in frozen.items()})
+        cov6_fixed = None if cov_moves else cov6_of()
+        if strategy.stats is not None:
+            strategy.stats = DensityStats(info["rows_out"], dev, absgrad=density.absgrad)
 
     cam = cam_rates = None  # the cameras' state and their (lr_trans, lr_rot, lr_exposure) per iteration from cameras.start on
     grid_on = cameras is not None and exposure_mode(cameras.exposure) == "bilagrid"
@@ -315,6 +357,9 @@ def refine_gaussians(means, scales, rotations, opacities, harmonics, images, c2w
         if it in strategy.events:
             with torch.no_grad():
                 event(it)
+        if it in prune_at:
+            with torch.no_grad():
+                prune_event(it)
         if it in strategy.resets and "opacities" in free:
             with torch.no_grad():
                 p = float(density.reset_opacity)
@@ -359,10 +404,14 @@ def refine_gaussians(means, scales, rotations, opacities, harmonics, images, c2w
             if lambdas_depth is not None:
                 depth_losses.append(float(d_loss.detach()))
     with torch.no_grad():
+        if prune is not None and prune.final and int(iters) > 0:
+            prune_event(int(iters))
         out = {k: value(k).detach().clone() for k in FIELDS}
         out["covariances"] = covariances_from(out["rotations"], out["scales"])
         if density is not None:
             out["density_events"] = events
+        if prune is not None:
+            out["prune_events"] = prune_events
         if lambdas_depth is not None:
             out["depth_losses"] = depth_losses
         if hip:
