@@ -389,6 +389,24 @@ int siu3r_raster_project_c2w(const siu3r_raster_cam* cams_host, int V, void* cam
                              int64_t G, const float* means, const float* cov, int cov_stride, const float* opacities, const float* colors,
                              int channels, int sh_planar, float* rec, int32_t* radii, int32_t* rect, int32_t* tiles_touched, uint32_t* keys,
                              uint64_t* stats, void* stream);
+/* ---- anti-aliased projection, 3DGS family (the 2-D filter of Mip-Splatting, Yu et al. 2024: upstream 3DGS's
+ * GaussianRasterizationSettings.antialiasing; additions, ABI version unchanged).  siu3r_raster_project / siu3r_raster_project_c2w with one
+ * more argument, comp, in front of the stream.  Per (view, Gaussian), with c00', c01, c11' the 2-D covariance entries BEFORE the camera's
+ * dilation B is added to the diagonal (the values themselves, not c00 - B), det1 the determinant of the dilated covariance (what the conic
+ * is divided by) and det0 = c00' c11' - c01^2 in Kahan's form (the rounding error of c01 * c01 recovered by one fma: a thin diagonal splat
+ * cancels badly in the naive form):
+ *   comp = sqrtf(fmaxf(2.5e-5f, det0 / det1)),   rec[.., 7] = opacity * comp   (where the rect is non-empty; elsewhere rec[.., 7] = opacity)
+ * so that the dilated footprint integrates to what the undilated one does (comp sqrt(det1) = sqrt(det0)) instead of growing brighter; the
+ * floor is upstream's.  comp [V, G] fp32 (optional, NULL = not wanted) receives the factor where the rect is non-empty and 0 elsewhere.
+ * The other eleven record slots, radii, rect, tiles_touched, keys and stats are the bits of the classic call; sort, bin, the composites,
+ * their backwards and siu3r_raster_contrib read the record's opacity and follow without change.  Mode 0 only: a mode-1 view array is refused. */
+int siu3r_raster_project_aa(const siu3r_raster_cam* cams_host, int V, void* cams_dev, int64_t G, const float* means, const float* cov,
+                            int cov_stride, const float* opacities, const float* colors, int channels, int sh_planar, float* rec,
+                            int32_t* radii, int32_t* rect, int32_t* tiles_touched, uint32_t* keys, uint64_t* stats, float* comp, void* stream);
+int siu3r_raster_project_c2w_aa(const siu3r_raster_cam* cams_host, int V, void* cams_dev, const float* c2w_dev, const float* Kn_dev, float t_scale,
+                                int64_t G, const float* means, const float* cov, int cov_stride, const float* opacities, const float* colors,
+                                int channels, int sh_planar, float* rec, int32_t* radii, int32_t* rect, int32_t* tiles_touched, uint32_t* keys,
+                                uint64_t* stats, float* comp, void* stream);
 /* stage 2: per view, stable LSD radix sort (4 x 8 bits) of keys_a [V,G] with the Gaussian index as payload; keys_b / ids_a / ids_b
  * [V,G] ping-pong buffers; rs_hist i32 [V,256,nchunks_sort], rs_tot i32 [V,256]; stats: stage 1's counters (device).  Culled Gaussians
  * (key 0xffffffff) leave the sort in its first pass: the result is the (depth, id)-ordered list of the n = stats[v][0] VISIBLE Gaussians in
@@ -475,6 +493,16 @@ int siu3r_raster_project_bwd(const siu3r_raster_cam* cams_host, int V, const voi
                              int cov_stride, const float* opacities, const float* colors, int channels, int sh_planar, const int32_t* rect,
                              const float* grad, float* g_means, float* g_cov, float* g_opacities, float* g_colors, float* g_mean2d,
                              float* pose_part, void* stream);
+/* the same for a forward that projected with siu3r_raster_project_aa / _c2w_aa (an addition, ABI version unchanged): the gradient of the
+ * anti-aliased record on the branch the forward took.  g_opacities += comp * grad[OP]; where r = det0 / det1 > 2.5e-5,
+ * d loss / d comp = grad[OP] * opacity goes through d comp / d r = 0.5 / comp and d r / d (c00', c01, c11') = (B / det1^2) (c11' c11 +
+ * c01^2, -2 c01 (c00' + c11), c00' c00 + c01^2) (the quotient rule with det1 - det0 = B (c00' + c11' + B) cancelled by hand: sums of
+ * like-signed terms) into the 2-D covariance gradient, added to the conic's contribution in front of the one
+ * chain to the covariance, the Jacobian, the mean and the pose partial rows; on the floor comp is a constant and only the opacity term remains. */
+int siu3r_raster_project_bwd_aa(const siu3r_raster_cam* cams_host, int V, const void* cams_dev, int64_t G, const float* means, const float* cov,
+                                int cov_stride, const float* opacities, const float* colors, int channels, int sh_planar, const int32_t* rect,
+                                const float* grad, float* g_means, float* g_cov, float* g_opacities, float* g_colors, float* g_mean2d,
+                                float* pose_part, void* stream);
 int64_t siu3r_raster_pose_partial_rows(int64_t G);
 /* pose_part [nrows, V, 6] -> g_pose [V, 6] = (rho, theta) per view */
 int siu3r_raster_pose_reduce(int V, int64_t nrows, const float* pose_part, float* g_pose, void* stream);
@@ -739,6 +767,30 @@ int siu3r_bilagrid_apply_bwd(const float* in, const int64_t* in_strides, const f
  * supported).  Deterministic; nothing allocates or synchronises with the host. */
 int64_t siu3r_bilagrid_tv_ws(int V, int L, int Gh, int Gw);
 int siu3r_bilagrid_tv(const float* grids, int V, int L, int Gh, int Gw, float scale, float* g_grids, void* ws, float* value, void* stream);
+
+/* ---- the 3-D smoothing filter of Mip-Splatting (csrc/mip_filter.hip; additions, ABI version unchanged) ----
+ * filter [G]: the radius below which the training cameras cannot sample a Gaussian.  c2w_dev [V,4,4] camera-to-world (fourth row taken as
+ * (0, 0, 0, 1)) and Kn_dev [V,3,3] NORMALISED intrinsics are row-major fp32 DEVICE tensors (no pose value is read on the host; the
+ * world->camera rows are derived in fp64 and rounded once); width, height: the training frame; means [G,3].  With (x, y, z) the
+ * camera-space point of a mean, fx, fy, cx, cy = Kn * (width, height), view v SEES the Gaussian when z > z_near and
+ * fx x / z + cx lies in [-margin W, (1 + margin) W] and fy y / z + cy in [-margin H, (1 + margin) H] (the principal point is Kn's;
+ * Mip-Splatting assumes the image centre).  d = the smallest z over the views that see it; a Gaussian no view sees (a NaN mean included)
+ * takes the LARGEST d of the seen ones; focal = the largest fx over the views:
+ *   filter = (sqrtf(variance) * d) / focal          (Mip-Splatting: z_near 0.2, margin 0.15, variance 0.2)
+ * and all zeros when no view sees any Gaussian.  The largest d is a maximum over bit patterns: two calls give the same bits.
+ * ws: siu3r_mip_filter3d_ws(V) BYTES on the device, 4-byte aligned.  z_near >= 0, margin >= 0, variance > 0.  Three launches; nothing
+ * allocates or synchronises with the host.  G == 0 writes nothing. */
+int64_t siu3r_mip_filter3d_ws(int V);
+int siu3r_mip_filter3d(const float* c2w_dev, const float* Kn_dev, int V, int width, int height, const float* means, int64_t G, float z_near,
+                       float margin, float variance, float* filter, void* ws, void* stream);
+/* the filter applied to ACTIVATED scales [G,3] and opacities [G] (one launch):
+ *   scales_f[i] = sqrtf(s_i^2 + f^2),   opac_f = o * (q_0 * q_1) * q_2,   q_i = |s_i| / scales_f[i]   (= sqrt(s_i^2 / (s_i^2 + f^2)); 1 where
+ * s_i = f = 0): the ratio is formed per axis, neither prod s_i^2 nor prod (s_i^2 + f^2) is.  scales_f must not alias scales. */
+int siu3r_mip_apply(const float* scales, const float* opacities, const float* filter, int64_t G, float* scales_f, float* opac_f, void* stream);
+/* its backward (one launch): g_scales[i] = g_scales_f[i] s_i / scales_f[i] + g_opac_f o (prod_{j != i} q_j) sign(s_i) (f / scales_f[i])^2 /
+ * scales_f[i] (0 where scales_f[i] = 0), g_opac = g_opac_f (q_0 * q_1) * q_2.  The filter gets no gradient. */
+int siu3r_mip_apply_bwd(const float* scales, const float* opacities, const float* filter, const float* g_scales_f, const float* g_opac_f, int64_t G,
+                        float* g_scales, float* g_opac, void* stream);
 
 #ifdef __cplusplus
 }

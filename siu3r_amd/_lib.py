@@ -154,6 +154,13 @@ SIGNATURES = {
     "siu3r_blend_background_dp": [_P, _P, _P, _I, _L, _P],
     "siu3r_raster_project_dp": [C.POINTER(RasterCam), _I, _P, _P, _P, _L, _P, _P, _I, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P],
     "siu3r_raster_project_c2w": [C.POINTER(RasterCam), _I, _P, _P, _P, _F, _L, _P, _P, _I, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P],
+    "siu3r_raster_project_aa": [C.POINTER(RasterCam), _I, _P, _L, _P, _P, _I, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P],
+    "siu3r_raster_project_c2w_aa": [C.POINTER(RasterCam), _I, _P, _P, _P, _F, _L, _P, _P, _I, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P],
+    "siu3r_raster_project_bwd_aa": [C.POINTER(RasterCam), _I, _P, _L, _P, _P, _I, _P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P],
+    "siu3r_mip_filter3d_ws": [_I],
+    "siu3r_mip_filter3d": [_P, _P, _I, _I, _I, _P, _L, _F, _F, _F, _P, _P, _P],
+    "siu3r_mip_apply": [_P, _P, _P, _L, _P, _P, _P],
+    "siu3r_mip_apply_bwd": [_P, _P, _P, _P, _P, _L, _P, _P, _P],
     "siu3r_raster_composite_rgb_bwd": [C.POINTER(RasterCam), _I, _P, _L, _P, _P, _L, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "siu3r_raster_composite_rgb_bwd_abs": [C.POINTER(RasterCam), _I, _P, _L, _P, _P, _L, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P],
     "siu3r_raster_contrib": [C.POINTER(RasterCam), _I, _P, _L, _P, _P, _L, _P, _P, _P, _P, _P],
@@ -206,6 +213,7 @@ _RESTYPES["siu3r_gaussian_adam_ws"] = C.c_int64
 _RESTYPES["siu3r_mcmc_ws"] = C.c_int64
 _RESTYPES["siu3r_exposure_ws"] = C.c_int64
 _RESTYPES["siu3r_bilagrid_tv_ws"] = C.c_int64
+_RESTYPES["siu3r_mip_filter3d_ws"] = C.c_int64
 
 _lib = None
 

@@ -16,7 +16,8 @@ gradient holders of the fork's camera update: the render uses `viewmatrix` as gi
 perturbation of world->camera, w2c <- exp(xi^) w2c with xi = (rho, theta) in se(3), taken at xi = 0 (`projmatrix` moves with the pose;
 `campos`, the SH view origin, is held fixed).  The caller folds the step into the pose and zeroes the holders.  `means2D`, when it
 requires grad, receives the screen-space gradient of upstream 3DGS: d loss / d NDC = the pixel gradient x (W/2, H/2) in its first two
-columns.  Semantics at the kinks: INTEGRATION.md seam 2."""
+columns.  `antialiasing` (the last settings field of current upstream 3DGS) selects the anti-aliased projection,
+raster.rasterize_views_k2(antialiased=True).  Semantics at the kinks: INTEGRATION.md seam 2."""
 from __future__ import annotations
 
 from typing import NamedTuple, Optional
@@ -40,6 +41,7 @@ class GaussianRasterizationSettings(NamedTuple):
     campos: Optional[torch.Tensor] = None
     prefiltered: bool = False
     debug: bool = False
+    antialiasing: bool = False
 
 
 def make_cam(s: GaussianRasterizationSettings, sh_band4: bool = False) -> "raster.RasterCam":
@@ -83,7 +85,8 @@ class GaussianRasterizer:
             scale = torch.ones(means2D.shape[-1], dtype=means2D.dtype, device=means2D.device)
             scale[0], scale[1] = 0.5 * s.image_width, 0.5 * s.image_height
             m2d = means2D * scale
-        o = raster.rasterize_views_k2([cam], means3D, cov3D_precomp, shs, opacities.reshape(-1), pose_delta=pose_delta, means2d=m2d)
+        o = raster.rasterize_views_k2([cam], means3D, cov3D_precomp, shs, opacities.reshape(-1), pose_delta=pose_delta, means2d=m2d,
+                                      antialiased=bool(s.antialiasing))
         return o["image"][0], o["radii"][0][:, 0].contiguous(), o["depth"][0][None], o["opacity"][0][None], o["n_touched"][0]
 
     __call__ = forward

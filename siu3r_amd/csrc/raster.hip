@@ -80,11 +80,15 @@ enum { ST_GV = 0, ST_D = 1, ST_E = 2, ST_FLAGS = 3, ST_N = 4 };
 // sh_planar 0: colors [G, ncoef, 3] (the layout the reference hands to the CUDA rasterizer, cuda_splatting.py:65); 1: [G, 3, ncoef]
 // (Gaussians.harmonics as stored: no repacking copy in front of the renderer).
 constexpr int PV = 16;  // views per projection chunk (blockIdx.y)
+// AA (compile time, mode-0 cameras only: the launcher refuses others): the anti-aliased record of Mip-Splatting's 2-D filter.  The opacity slot
+// holds opacity * comp, comp = sqrt(max(2.5e-5, det0 / det)) with det0 the determinant of the 2-D covariance BEFORE the dilation (Kahan form:
+// conic_det) and det the one the conic is divided by; comp [V, G] (optional) receives it, 0 where the rect is empty.  Nothing else changes.
+template <bool AA>
 __global__ __launch_bounds__(256) void project_kernel(const Cam* __restrict__ cams, int nviews, int nf_chunk, int64_t G, const float* __restrict__ means,
                                                       const float* __restrict__ cov, int cov_stride, const float* __restrict__ opac,
                                                       const float* __restrict__ colors, int channels, int sh_planar, float* __restrict__ rec,
                                                       int32_t* __restrict__ radii, int32_t* __restrict__ rect, int32_t* __restrict__ tiles_touched,
-                                                      uint32_t* __restrict__ keys, unsigned long long* __restrict__ stats) {
+                                                      uint32_t* __restrict__ keys, unsigned long long* __restrict__ stats, float* __restrict__ comp) {
   // One thread per Gaussian, looping over the (up to PV) views of blockIdx.y's chunk: mean, covariance, opacity and the 300-byte SH
   // block are read ONCE per chunk instead of once per view (six target views of a pair scene re-read 1.26 GB of SH coefficients
   // before: the kernel was HBM-bound on traffic that the algorithm does not need).  The SH block is fetched at the first view that
@@ -109,7 +113,7 @@ __global__ __launch_bounds__(256) void project_kernel(const Cam* __restrict__ ca
     const int64_t o = (int64_t)v * G + g;
     const float* V = c.w2c;
     int rx_i = 0, ry_i = 0, tx0 = 0, ty0 = 0, tx1 = 0, ty1 = 0;
-    float mx = 0.f, my = 0.f, ca = 0.f, cb = 0.f, cc = 0.f;
+    float mx = 0.f, my = 0.f, ca = 0.f, cb = 0.f, cc = 0.f, cmp = 0.f;
     const float tx = V[0] * m[0] + V[1] * m[1] + V[2] * m[2] + V[3];
     const float ty = V[4] * m[0] + V[5] * m[1] + V[6] * m[2] + V[7];
     const float tz = V[8] * m[0] + V[9] * m[1] + V[10] * m[2] + V[11];
@@ -167,6 +171,13 @@ __global__ __launch_bounds__(256) void project_kernel(const Cam* __restrict__ ca
         if (c.mode == 0) rx_i = ry_i = 0;
         break;
       }
+      if constexpr (AA) {
+        // the sums project_cov2d adds the blur to, formed again beside it (the same operations on the same inputs: the same bits);
+        // a thin diagonal splat cancels badly in c00' c11' - c01^2, hence the Kahan form
+        const float c00p = p.a[0] * p.t0[0] + p.a[1] * p.t0[1] + p.a[2] * p.t0[2];
+        const float c11p = p.b[0] * p.t1[0] + p.b[1] * p.t1[1] + p.b[2] * p.t1[2];
+        cmp = sqrtf(fmaxf(2.5e-5f, conic_det(c00p, c01, c11p) / det));
+      }
       valid = true;
     } while (false);
     ntiles = valid ? (tx1 - tx0) * (ty1 - ty0) : 0;
@@ -176,7 +187,12 @@ __global__ __launch_bounds__(256) void project_kernel(const Cam* __restrict__ ca
     *(int4*)(rect + 4 * o) = valid ? make_int4(tx0, ty0, tx1, ty1) : make_int4(0, 0, 0, 0);
     float4* rp = (float4*)(rec + 12 * o);
     rp[0] = make_float4(mx, my, tz, 0.f);
-    rp[1] = make_float4(ca, cb, cc, opacity);
+    if constexpr (AA) {
+      rp[1] = make_float4(ca, cb, cc, valid ? opacity * cmp : opacity);
+      if (comp) comp[o] = cmp;  // (0 unless valid)
+    } else {
+      rp[1] = make_float4(ca, cb, cc, opacity);
+    }
     // positive floats order like their bit patterns; culled Gaussians sort behind every visible one
     // (0xffffffff is reserved for "culled": the sort drops exactly those keys and trusts stats[ST_GV] = the number of valid flags, so
     // the two must agree by construction -- a valid Gaussian whose depth has that bit pattern, a NaN payload, is clamped below it)
@@ -1386,7 +1402,8 @@ __global__ void cam_pose_c2w_kernel(Cam* cams, int V, const float* c2w, const fl
 static int project_impl(const siu3r_raster_cam* cams_host, int V, void* cams_dev, int64_t G, const float* means, const float* cov,
                         int cov_stride, const float* opacities, const float* colors, int channels, int sh_planar, float* rec,
                         int32_t* radii, int32_t* rect, int32_t* tiles_touched, uint32_t* keys, uint64_t* stats, void* stream,
-                        const float* viewmats_dev, const float* Ks_dev, const float* c2w_dev = nullptr, float t_scale = 1.f);
+                        const float* viewmats_dev, const float* Ks_dev, const float* c2w_dev = nullptr, float t_scale = 1.f, bool aa = false,
+                        float* comp = nullptr);
 
 extern "C" int siu3r_raster_project(const siu3r_raster_cam* cams_host, int V, void* cams_dev, int64_t G, const float* means, const float* cov,
                                     int cov_stride, const float* opacities, const float* colors, int channels, int sh_planar, float* rec,
@@ -1417,11 +1434,31 @@ extern "C" int siu3r_raster_project_c2w(const siu3r_raster_cam* cams_host, int V
                       stream, nullptr, Kn_dev, c2w_dev, t_scale);
 }
 
+extern "C" int siu3r_raster_project_aa(const siu3r_raster_cam* cams_host, int V, void* cams_dev, int64_t G, const float* means, const float* cov,
+                                       int cov_stride, const float* opacities, const float* colors, int channels, int sh_planar, float* rec,
+                                       int32_t* radii, int32_t* rect, int32_t* tiles_touched, uint32_t* keys, uint64_t* stats, float* comp, void* stream) {
+  return project_impl(cams_host, V, cams_dev, G, means, cov, cov_stride, opacities, colors, channels, sh_planar, rec, radii, rect, tiles_touched, keys, stats,
+                      stream, nullptr, nullptr, nullptr, 1.f, true, comp);
+}
+
+extern "C" int siu3r_raster_project_c2w_aa(const siu3r_raster_cam* cams_host, int V, void* cams_dev, const float* c2w_dev, const float* Kn_dev, float t_scale,
+                                           int64_t G, const float* means, const float* cov, int cov_stride, const float* opacities, const float* colors,
+                                           int channels, int sh_planar, float* rec, int32_t* radii, int32_t* rect, int32_t* tiles_touched, uint32_t* keys,
+                                           uint64_t* stats, float* comp, void* stream) {
+  SIU3R_CHECK(c2w_dev && Kn_dev, "raster_project_c2w_aa: null pose pointer");
+  SIU3R_CHECK(cams_host && V > 0 && cams_host[0].mode == 0, "raster_project_c2w_aa: the anti-aliased projection covers the 3DGS family (mode 0)");
+  for (int v = 0; v < V; ++v)
+    SIU3R_CHECK(cams_host[v].k2_near > 0.f && cams_host[v].k2_far > cams_host[v].k2_near, "raster_project_c2w_aa: view %d needs 0 < k2_near < k2_far", v);
+  return project_impl(cams_host, V, cams_dev, G, means, cov, cov_stride, opacities, colors, channels, sh_planar, rec, radii, rect, tiles_touched, keys, stats,
+                      stream, nullptr, Kn_dev, c2w_dev, t_scale, true, comp);
+}
+
 static int project_impl(const siu3r_raster_cam* cams_host, int V, void* cams_dev, int64_t G, const float* means, const float* cov,
                         int cov_stride, const float* opacities, const float* colors, int channels, int sh_planar, float* rec,
                         int32_t* radii, int32_t* rect, int32_t* tiles_touched, uint32_t* keys, uint64_t* stats, void* stream,
-                        const float* viewmats_dev, const float* Ks_dev, const float* c2w_dev, float t_scale) {
+                        const float* viewmats_dev, const float* Ks_dev, const float* c2w_dev, float t_scale, bool aa, float* comp) {
   if (int rc = check_views(cams_host, V, "raster_project")) return rc;
+  SIU3R_CHECK(!aa || cams_host[0].mode == 0, "raster_project_aa: the anti-aliased projection covers the 3DGS family (mode 0)");
   SIU3R_CHECK(cams_dev && stats, "raster_project: null pointer");
   SIU3R_CHECK(G >= 0 && G < (1ll << 31), "raster_project: G = %ld out of range", (long)G);
   SIU3R_CHECK(G == 0 || (means && cov && opacities && rec && radii && rect && tiles_touched && keys), "raster_project: null per-Gaussian pointer");
@@ -1448,9 +1485,15 @@ static int project_impl(const siu3r_raster_cam* cams_host, int V, void* cams_dev
     const int ncf = (deg > 3 && cams_host[v].sh_band4) ? 25 : (deg > 2 ? 16 : (deg > 1 ? 9 : (deg > 0 ? 4 : 1)));
     if (cams_host[v].mode == 0 && ncf * 3 > nf_chunk) nf_chunk = ncf * 3;
   }
-  if (G > 0)
-    hipLaunchKernelGGL(project_kernel, dim3((unsigned)cdiv64(G, 256), (V + PV - 1) / PV), dim3(256), 0, s, (const Cam*)cams_dev, V, nf_chunk, G, means, cov,
-                       cov_stride, opacities, colors, channels, sh_planar, rec, radii, rect, tiles_touched, keys, (unsigned long long*)stats);
+  if (G > 0) {
+    const dim3 grid((unsigned)cdiv64(G, 256), (V + PV - 1) / PV);
+    if (aa)
+      hipLaunchKernelGGL(project_kernel<true>, grid, dim3(256), 0, s, (const Cam*)cams_dev, V, nf_chunk, G, means, cov, cov_stride, opacities, colors, channels,
+                         sh_planar, rec, radii, rect, tiles_touched, keys, (unsigned long long*)stats, comp);
+    else
+      hipLaunchKernelGGL(project_kernel<false>, grid, dim3(256), 0, s, (const Cam*)cams_dev, V, nf_chunk, G, means, cov, cov_stride, opacities, colors, channels,
+                         sh_planar, rec, radii, rect, tiles_touched, keys, (unsigned long long*)stats, (float*)nullptr);
+  }
   SIU3R_LAUNCH_CHECK("siu3r_raster_project");
   return 0;
 }

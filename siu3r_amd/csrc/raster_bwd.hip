@@ -206,6 +206,14 @@ __global__ __launch_bounds__(256) void composite_rgb_bwd_kernel(const Cam* __res
 // grad [V, G, GR_N] (composite backward) -> g_means [G,3], g_cov [G, cov_stride], g_opac [G], g_colors (the layout of colors),
 // g_mean2d [V, G, 2] (optional: the pixel-space mean gradient), pose_part [gridDim.x, V, 6] (optional: per-workgroup sums of
 // d loss / d (rho, theta) of a left perturbation w2c <- exp(xi^) w2c).
+// AA (compile time): the backward of project_kernel<true>, whose record opacity is opacity * comp, comp = sqrt(max(2.5e-5, r)), r = det0 / det
+// (det0 = conic_det of the 2-D covariance before the dilation B, det = the dilated one's).  g_opac takes comp * grad[OP]; above the floor
+// d loss / d comp = grad[OP] * opacity goes through d comp / d r = 0.5 / comp and, with det - det0 = B (c00' + c11' + B) used to cancel
+// the leading terms by hand (the quotient rule's (c11' det - det0 c11) loses c00' / B digits on a large splat),
+//   d r / d c00' = B (c11' c11 + c01^2) / det^2,  d r / d c11' = B (c00' c00 + c01^2) / det^2,  d r / d c01 = -2 c01 B (c00' + c11) / det^2
+// (sums of like-signed terms) into the 2-D covariance gradient, next to the conic's, in front of the one chain (project_cov2d_bwd<true>).
+// On the floor comp is a constant.
+template <bool AA>
 __global__ __launch_bounds__(256) void project_bwd_kernel(const Cam* __restrict__ cams, int V, int64_t G, const float* __restrict__ means,
                                                           const float* __restrict__ cov, int cov_stride, const float* __restrict__ opac,
                                                           const float* __restrict__ colors, int channels, int sh_planar,
@@ -242,7 +250,27 @@ __global__ __launch_bounds__(256) void project_bwd_kernel(const Cam* __restrict_
       const Lens lens = lens_k2(c);
       const float fx = lens.fx, fy = lens.fy;
       const Cov2D p = project_cov2d(lens, W, tx, ty, tz, S);
-      const Cov2DGrad q = project_cov2d_bwd(p, W, gr[GR_CA], gr[GR_CB], gr[GR_CC], gS);
+      Cov2DGrad q;
+      float cmp = 1.0f;
+      if constexpr (AA) {
+        // comp as the forward formed it (the same operations: the same bits, so the same side of the floor)
+        const float c00p = p.a[0] * p.t0[0] + p.a[1] * p.t0[1] + p.a[2] * p.t0[2];
+        const float c11p = p.b[0] * p.t1[0] + p.b[1] * p.t1[1] + p.b[2] * p.t1[2];
+        const float r_ = conic_det(c00p, p.c01, c11p) / p.det;
+        cmp = sqrtf(fmaxf(2.5e-5f, r_));
+        float e00 = 0.f, e01 = 0.f, e11 = 0.f;
+        if (r_ > 2.5e-5f) {
+          const float rdet = 1.0f / p.det;
+          const float dr = ((gr[GR_OP] * opac[g]) * (0.5f / cmp)) * ((lens.blur * rdet) * rdet);  // d loss / d r times B / det^2
+          const float c01sq = p.c01 * p.c01;
+          e00 = dr * (c11p * p.c11 + c01sq);
+          e11 = dr * (c00p * p.c00 + c01sq);
+          e01 = dr * (-2.0f * p.c01 * (c00p + p.c11));
+        }
+        q = project_cov2d_bwd<true>(p, W, gr[GR_CA], gr[GR_CB], gr[GR_CC], gS, e00, e01, e11);
+      } else {
+        q = project_cov2d_bwd(p, W, gr[GR_CA], gr[GR_CB], gr[GR_CC], gS);
+      }
       const float W0[3] = {W[0], W[1], W[2]}, W1[3] = {W[4], W[5], W[6]}, W2[3] = {W[8], W[9], W[10]};
       // d loss / d W through the covariance only (rows), for the rotation part of the pose gradient
       float GW[3][3];
@@ -275,7 +303,8 @@ __global__ __launch_bounds__(256) void project_bwd_kernel(const Cam* __restrict_
       const float dp[3] = {dtx, dty, dtz};
 #pragma unroll
       for (int i = 0; i < 3; ++i) gm[i] += W0[i] * dp[0] + W1[i] * dp[1] + W2[i] * dp[2] + gmp[i];
-      gop += gr[GR_OP];
+      if constexpr (AA) gop += cmp * gr[GR_OP];
+      else gop += gr[GR_OP];
       if (pose_part) {
         // camera-space point gradient of the whole view: dp + W^-T gmp (P = proj w2c: the matching P moves with the pose);
         // W^-T = cofactor(W) / det(W), cofactor rows = cross products of W's rows
@@ -393,26 +422,43 @@ extern "C" int siu3r_raster_composite_rgb_bwd_k3(const siu3r_raster_cam* cams_ho
                                  nullptr, g_alphas, grad, nullptr, stream);
 }
 
+// the launcher body of the two projection backwards (AA: the anti-aliased record's)
+template <bool AA>
+static int project_bwd(const char* who, const siu3r_raster_cam* cams_host, int V, const void* cams_dev, int64_t G, const float* means, const float* cov,
+                       int cov_stride, const float* opacities, const float* colors, int channels, int sh_planar, const int32_t* rect, const float* grad,
+                       float* g_means, float* g_cov, float* g_opacities, float* g_colors, float* g_mean2d, float* pose_part, void* stream) {
+  if (int rc = check_views(cams_host, V, 0, who)) return rc;
+  SIU3R_CHECK(G >= 0 && G < (1ll << 31), "%s: G = %ld out of range", who, (long)G);
+  SIU3R_CHECK(cams_dev && (G == 0 || (means && cov && opacities && colors && rect && grad && g_means && g_cov && g_opacities && g_colors)),
+              "%s: null pointer", who);
+  SIU3R_CHECK(cov_stride == 6 || cov_stride == 9, "%s: cov_stride must be 6 or 9", who);
+  SIU3R_CHECK(!sh_planar || channels == 25, "%s: the planar SH layout needs 25 coefficients", who);
+  SIU3R_CHECK(channels >= 1 && channels <= 25, "%s: 1 .. 25 colour coefficients (got %d)", who, channels);
+  for (int v = 0; v < V; ++v)
+    SIU3R_CHECK(cams_host[v].sh_degree < 0 ? (channels == 1 && !sh_planar) : channels >= (cams_host[v].sh_degree + 1) * (cams_host[v].sh_degree + 1),
+                "%s: colour coefficients do not match sh_degree", who);
+  if (G == 0) return 0;
+  hipStream_t s = (hipStream_t)stream;
+  hipLaunchKernelGGL(project_bwd_kernel<AA>, dim3((unsigned)cdiv64(G, 256)), dim3(256), 0, s, (const Cam*)cams_dev, V, G, means, cov, cov_stride, opacities, colors,
+                     channels, sh_planar, rect, grad, g_means, g_cov, g_opacities, g_colors, g_mean2d, pose_part);
+  SIU3R_LAUNCH_CHECK(who);
+  return 0;
+}
+
 extern "C" int siu3r_raster_project_bwd(const siu3r_raster_cam* cams_host, int V, const void* cams_dev, int64_t G, const float* means, const float* cov,
                                         int cov_stride, const float* opacities, const float* colors, int channels, int sh_planar, const int32_t* rect,
                                         const float* grad, float* g_means, float* g_cov, float* g_opacities, float* g_colors, float* g_mean2d,
                                         float* pose_part, void* stream) {
-  if (int rc = check_views(cams_host, V, 0, "raster_project_bwd")) return rc;
-  SIU3R_CHECK(G >= 0 && G < (1ll << 31), "raster_project_bwd: G = %ld out of range", (long)G);
-  SIU3R_CHECK(cams_dev && (G == 0 || (means && cov && opacities && colors && rect && grad && g_means && g_cov && g_opacities && g_colors)),
-              "raster_project_bwd: null pointer");
-  SIU3R_CHECK(cov_stride == 6 || cov_stride == 9, "raster_project_bwd: cov_stride must be 6 or 9");
-  SIU3R_CHECK(!sh_planar || channels == 25, "raster_project_bwd: the planar SH layout needs 25 coefficients");
-  SIU3R_CHECK(channels >= 1 && channels <= 25, "raster_project_bwd: 1 .. 25 colour coefficients (got %d)", channels);
-  for (int v = 0; v < V; ++v)
-    SIU3R_CHECK(cams_host[v].sh_degree < 0 ? (channels == 1 && !sh_planar) : channels >= (cams_host[v].sh_degree + 1) * (cams_host[v].sh_degree + 1),
-                "raster_project_bwd: colour coefficients do not match sh_degree");
-  if (G == 0) return 0;
-  hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(project_bwd_kernel, dim3((unsigned)cdiv64(G, 256)), dim3(256), 0, s, (const Cam*)cams_dev, V, G, means, cov, cov_stride, opacities, colors,
-                     channels, sh_planar, rect, grad, g_means, g_cov, g_opacities, g_colors, g_mean2d, pose_part);
-  SIU3R_LAUNCH_CHECK("siu3r_raster_project_bwd");
-  return 0;
+  return project_bwd<false>("raster_project_bwd", cams_host, V, cams_dev, G, means, cov, cov_stride, opacities, colors, channels, sh_planar, rect, grad, g_means,
+                            g_cov, g_opacities, g_colors, g_mean2d, pose_part, stream);
+}
+
+extern "C" int siu3r_raster_project_bwd_aa(const siu3r_raster_cam* cams_host, int V, const void* cams_dev, int64_t G, const float* means, const float* cov,
+                                           int cov_stride, const float* opacities, const float* colors, int channels, int sh_planar, const int32_t* rect,
+                                           const float* grad, float* g_means, float* g_cov, float* g_opacities, float* g_colors, float* g_mean2d,
+                                           float* pose_part, void* stream) {
+  return project_bwd<true>("raster_project_bwd_aa", cams_host, V, cams_dev, G, means, cov, cov_stride, opacities, colors, channels, sh_planar, rect, grad,
+                           g_means, g_cov, g_opacities, g_colors, g_mean2d, pose_part, stream);
 }
 
 extern "C" int64_t siu3r_raster_pose_partial_rows(int64_t G) { return G > 0 ? cdiv64(G, 256) : 0; }

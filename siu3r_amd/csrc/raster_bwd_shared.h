@@ -53,18 +53,28 @@ __global__ __launch_bounds__(256) void rows_reduce_kernel(int V, int64_t nblk, c
 
 // ---- projection backward: what both camera modes share -------------------------------------------------------------------------------
 // d loss / d conic (gca, gcb, gcc) -> through the conic inverse and the 2-D covariance M Sigma M^T (p: the forward chain, project_cov2d)
-// to the rows of M (dt0, dt1), the Jacobian entries (dj..) and, added into gS[6], the Gaussian's covariance
+// to the rows of M (dt0, dt1), the Jacobian entries (dj..) and, added into gS[6], the Gaussian's covariance.
+// DIRECT (compile time): e00, e01, e11 = d loss / d (c00, c01, c11) that reaches the 2-D covariance NOT through the conic (the anti-aliased
+// projection's opacity compensation; c01 counted once, as d01 is) are added to the conic's contribution before the chain, so that one chain
+// carries both.  Without it the three arguments are not read and the code is the one it was.
 struct Cov2DGrad {
   float dt0[3], dt1[3], dj00, dj02, dj11, dj12;
 };
-__device__ __forceinline__ Cov2DGrad project_cov2d_bwd(const Cov2D& p, const float* W, float gca, float gcb, float gcc, float* gS) {
+template <bool DIRECT = false>
+__device__ __forceinline__ Cov2DGrad project_cov2d_bwd(const Cov2D& p, const float* W, float gca, float gcb, float gcc, float* gS, float e00 = 0.f,
+                                                       float e01 = 0.f, float e11 = 0.f) {
   const float* t0 = p.t0;
   const float* t1 = p.t1;
   const float rdet = 1.0f / p.det;
   const float ca = p.c11 * rdet, cb = -p.c01 * rdet, cc = p.c00 * rdet;
   // conic inverse
   const float dLddet = -(gca * ca + gcb * cb + gcc * cc) * rdet;
-  const float d00 = gcc * rdet + dLddet * p.c11, d11 = gca * rdet + dLddet * p.c00, d01 = -gcb * rdet - 2.0f * dLddet * p.c01;
+  float d00 = gcc * rdet + dLddet * p.c11, d11 = gca * rdet + dLddet * p.c00, d01 = -gcb * rdet - 2.0f * dLddet * p.c01;
+  if constexpr (DIRECT) {
+    d00 += e00;
+    d01 += e01;
+    d11 += e11;
+  }
   // 2-D covariance = M Sigma M^T (+ blur), M = J W (rows t0, t1)
   Cov2DGrad q;
 #pragma unroll

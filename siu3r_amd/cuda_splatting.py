@@ -46,7 +46,7 @@ def get_projection_matrix(near, far, fov_x, fov_y) -> torch.Tensor:
 def render_cuda(extrinsics, intrinsics, near, far, image_shape, background_color, gaussian_means, gaussian_covariances,
                 gaussian_sh_coefficients, gaussian_opacities, use_sh: bool = True, cam_rot_delta=None, cam_trans_delta=None,
                 sh_band4: bool = False, return_aux: bool = False, entry_capacity=None, check_overflow=True, translation_scale: float = 1.0,
-                density_stats=None):
+                density_stats=None, antialiased: bool = False):
     """reference signature cuda_splatting.py:46-60 (batch = views).  Returns (images [b,3,h,w], depths [b,h,w]); return_aux adds the
     per-call outputs (radii, n_touched, opacity, binning state).  entry_capacity: optional size of the coarse-bin entry buffers (an
     overflow of the default bound is detected and the call repeated with the exact size).  check_overflow: True (synchronous, as the
@@ -61,7 +61,8 @@ def render_cuda(extrinsics, intrinsics, near, far, image_shape, background_color
     Views whose Gaussians are expanded from one tensor still render as one multi-view call; autograd sums their gradients.
     density_stats: a density.DensityStats that the backward fills with the densification statistics of this render (per-view position
     gradient norms, visibility counts, largest radii: raster.rasterize_views_k2); the views must then share ONE Gaussian set.  None, the
-    default, changes nothing."""
+    default, changes nothing.
+    antialiased: the anti-aliased projection (Mip-Splatting's 2-D filter: raster.rasterize_views_k2); False, the default, changes nothing."""
     assert use_sh or gaussian_sh_coefficients.shape[-1] == 1
     if (cam_rot_delta is None) != (cam_trans_delta is None):
         raise ValueError("pass cam_rot_delta and cam_trans_delta together (one se(3) update per view)")
@@ -115,7 +116,8 @@ def render_cuda(extrinsics, intrinsics, near, far, image_shape, background_color
         delta = None if cam_rot_delta is None else torch.cat((cam_trans_delta[i0:i1], cam_rot_delta[i0:i1]), dim=-1).float()
         out = raster.rasterize_views_k2(cams, gaussian_means[i0], gaussian_covariances[i0], sh_i if planar else sh_i.permute(0, 2, 1).contiguous(),
                                         gaussian_opacities[i0], want_n_touched=return_aux, entry_capacity=entry_capacity, sh_planar=planar,
-                                        check_overflow=check_overflow, pose_c2w=pose, pose_delta=delta, density_stats=density_stats)
+                                        check_overflow=check_overflow, pose_c2w=pose, pose_delta=delta, density_stats=density_stats,
+                                        **(dict(antialiased=True) if antialiased else {}))
         images.append(out["image"])
         depths.append(out["depth"])
         aux.append(out)

@@ -49,11 +49,12 @@ class ContributionStats:
 
 
 def gaussian_contributions(means, scales, rotations, opacities, c2w, Kn, near, far, image_shape, view_chunk: int = 8,
-                           translation_scale: float = 1.0) -> ContributionStats:
+                           translation_scale: float = 1.0, antialiased: bool = False) -> ContributionStats:
     """The contributions of one Gaussian set to V posed views, in the conventions of cuda_splatting.render_cuda and refine.refine_gaussians:
     means [G,3], scales [G,3], rotations [G,4] raw (x, y, z, w) quaternions, opacities [G] (all in their natural form, on the GPU); c2w
     [V,4,4] camera-to-world, Kn [V,3,3] (or [3,3]) normalised intrinsics, near / far floats (or [V]), image_shape (H, W).  The poses are
-    consumed on the device.  `view_chunk` views go through the rasterizer per call (it bounds the [V,G] temporaries)."""
+    consumed on the device.  `view_chunk` views go through the rasterizer per call (it bounds the [V,G] temporaries).  antialiased: the
+    weights of the anti-aliased render (raster.contributions_k2)."""
     if int(view_chunk) <= 0:
         raise ValueError(f"view_chunk must be positive, got {view_chunk}")
     dev = means.device
@@ -70,7 +71,8 @@ def gaussian_contributions(means, scales, rotations, opacities, c2w, Kn, near, f
         for v0 in range(0, V, int(view_chunk)):
             v1 = min(V, v0 + int(view_chunk))
             cams = [raster.make_cam_k2(None, None, None, None, None, (0.0, 0.0, 0.0), W, H, sh_degree=-1, near=near_v[v], far=far_v[v]) for v in range(v0, v1)]
-            stats.accumulate(raster.contributions_k2(cams, means, cov6, opacities, pose_c2w=(c2w[v0:v1], Kn[v0:v1], float(translation_scale))))
+            stats.accumulate(raster.contributions_k2(cams, means, cov6, opacities, pose_c2w=(c2w[v0:v1], Kn[v0:v1], float(translation_scale)),
+                                                     **(dict(antialiased=True) if antialiased else {})))
     return stats
 
 

@@ -119,6 +119,7 @@ class RasterState:
                  "pose_dev",  # the two device pose tensors of a "dp" / "c2w" call: like feat_ws kept here because launches read them asynchronously
                  "defer", "cap_d_hint",  # the caller checks for overflow later: nothing synchronises; pair capacity the lists start from
                  "feat_ws", "feat_ws_lists",  # workspace of the N-channel matrix-core composite, and whether it holds the per-quadrant lists
+                 "antialiased",  # the projection was the anti-aliased one (siu3r_raster_project_aa): a backward must differentiate that record
                  "_stats_host", "_tl")  # _tl: (tile_start_all [V,T+2], ids_all [V,cap_d], cap_d) once _lists() ran
 
     def __init__(self, **fields):
@@ -229,8 +230,10 @@ def _pose(V, dev, pose_dev=None, pose_c2w=None) -> _Pose:
 
 
 def _project_sort_bin(cams: Sequence[RasterCam], means, cov, opac, colors, channels, entry_capacity=None, check_overflow=True,
-                      sh_planar=False, pose: _Pose = _HOST_POSE) -> RasterState:
+                      sh_planar=False, pose: _Pose = _HOST_POSE, antialiased=False) -> RasterState:
     V, G, dev = len(cams), means.shape[0], means.device
+    if antialiased and (pose.kind == "dp" or any(c.mode != 0 for c in cams)):
+        raise ValueError("antialiased=True covers the 3DGS family (K2 cameras); the gsplat-family (K3) path has no anti-aliased mode")
     arr = _cam_array(cams)
     W, H = cams[0].width, cams[0].height
     geo = geometry(W, H, G)
@@ -244,7 +247,14 @@ def _project_sort_bin(cams: Sequence[RasterCam], means, cov, opac, colors, chann
     head = (arr, V, _p(st.cams_dev))
     tail = (G, _p(means), _p(cov), _cov_stride(cov), _p(opac), _p(colors), channels, int(bool(sh_planar)), _p(st.rec), _p(st.radii), _p(st.rect),
             _p(st.tiles_touched_all), _p(st.keys), _p(st.stats_dev), _stream())
-    if pose.kind == "host":
+    if antialiased:  # the same calls with the compensation in the record's opacity; the factor itself (comp) is not wanted here
+        st.antialiased = True
+        if pose.kind == "c2w":
+            st.pose_dev = (pose.a, pose.b)
+            check(lib.siu3r_raster_project_c2w_aa(*head, _p(pose.a), _p(pose.b), pose.t_scale, *tail[:-1], None, tail[-1]))
+        else:
+            check(lib.siu3r_raster_project_aa(*head, *tail[:-1], None, tail[-1]))
+    elif pose.kind == "host":
         check(lib.siu3r_raster_project(*head, *tail))
     else:
         st.pose_dev = (pose.a, pose.b)  # (kept with the state: the launches read them asynchronously)
@@ -333,13 +343,13 @@ def _with_retry(run, entry_capacity, check_overflow):
     return out
 
 
-def _render(cams, means, cov6, opacities, chan, channels, pose, entry_capacity, check_overflow, composite, sh_planar=False):
+def _render(cams, means, cov6, opacities, chan, channels, pose, entry_capacity, check_overflow, composite, sh_planar=False, antialiased=False):
     """The one render path (the entry points have checked the device).  chan: the call's colour block -- `channels` > 0: shs / rgb, which the
     projection reads into the records; 0: feats, which only the composite reads.  composite(st, chan): allocate outputs, launch, return the dict."""
     means, cov6, opacities, chan = (t.contiguous().float() for t in (means, cov6, opacities, chan))
 
     def run(cap):
-        st = _project_sort_bin(cams, means, cov6, opacities, chan if channels else None, channels, cap, check_overflow, sh_planar, pose)
+        st = _project_sort_bin(cams, means, cov6, opacities, chan if channels else None, channels, cap, check_overflow, sh_planar, pose, antialiased)
         return composite(st, chan)
 
     return _with_retry(run, entry_capacity, check_overflow)
@@ -393,8 +403,8 @@ def _grads_out(ctx, first, grads):
 
 
 def rasterize_views_k2(cams: Sequence[RasterCam], means, cov6, shs, opacities, want_n_touched=True, entry_capacity=None,
-                       check_overflow=True, sh_planar=False, pose_c2w=None, pose_delta=None, means2d=None, density_stats=None
-                       ) -> Dict[str, torch.Tensor]:
+                       check_overflow=True, sh_planar=False, pose_c2w=None, pose_delta=None, means2d=None, density_stats=None,
+                       antialiased=False) -> Dict[str, torch.Tensor]:
     """V views of one Gaussian set.  means [G,3]; cov6 [G,6] (upper triangle) or [G,3,3]; shs [G,ncoef,3], or with sh_planar
     [G,3,25] (Gaussians.harmonics as stored); opacities [G] (fp32, GPU) -> image [V,3,H,W], radii [V,G,2] i32, depth [V,H,W],
     opacity [V,H,W], n_touched [V,G] i32 (None when not wanted) + the call's state.
@@ -407,7 +417,12 @@ def rasterize_views_k2(cams: Sequence[RasterCam], means, cov6, shs, opacities, w
     gradient norms (scaled by V: DensityStats.accumulate), the visibility counts and the largest radii into it.  The forward does not
     look at it, and None (the default) leaves the backward exactly as it is without the keyword.  With density_stats.absgrad the composite
     backward is siu3r_raster_composite_rgb_bwd_abs and the norms are those of its abs_mean2d (AbsGS); every returned gradient, means2d's
-    included, stays the signed one."""
+    included, stays the signed one.
+    antialiased=True: the 2-D filter of Mip-Splatting (upstream 3DGS's `antialiasing`): every (view, Gaussian) opacity is multiplied by
+    sqrt(max(2.5e-5, det(Sigma2D) / det(Sigma2D + dilation I))) inside the projection (siu3r_raster_project_aa), so the dilation no longer
+    brightens a sub-pixel splat; everything behind the projection, n_touched and the backward included, follows the compensated record
+    (siu3r_raster_project_bwd_aa differentiates the factor).  False, the default, takes the calls it took without the keyword.  K3 cameras
+    with antialiased=True raise ValueError."""
     wants_grad = _wants_grad(means, cov6, shs, opacities, pose_delta, means2d)
     if wants_grad:
         _no_deferred(check_overflow)
@@ -418,8 +433,8 @@ def rasterize_views_k2(cams: Sequence[RasterCam], means, cov6, shs, opacities, w
     _gpu(means, cov6, shs, opacities)
     pose = _pose(len(cams), means.device, pose_c2w=pose_c2w)
     if not wants_grad:
-        return _rasterize_views_k2(cams, means, cov6, shs, opacities, want_n_touched, entry_capacity, check_overflow, sh_planar, pose)
-    render = lambda *gaussians: _rasterize_views_k2(cams, *gaussians, want_n_touched, entry_capacity, True, sh_planar, pose)
+        return _rasterize_views_k2(cams, means, cov6, shs, opacities, want_n_touched, entry_capacity, check_overflow, sh_planar, pose, antialiased)
+    render = lambda *gaussians: _rasterize_views_k2(cams, *gaussians, want_n_touched, entry_capacity, True, sh_planar, pose, antialiased)
     image, depth, opacity, radii, n_touched, st = _RasterizeK2.apply(render, sh_planar, density_stats, means, cov6, shs, opacities, pose_delta, means2d)
     return dict(image=image, radii=radii, depth=depth, opacity=opacity, n_touched=n_touched, state=st)
 
@@ -459,9 +474,9 @@ class _RasterizeK2(torch.autograd.Function):
             g_m2d = torch.empty((V, G, 2), dtype=torch.float32, device=dev)  # (the statistics go by the radii, never by an unwritten row)
         rows = int(lib.siu3r_raster_pose_partial_rows(G))
         part = torch.empty((max(rows, 1), V, 6), dtype=torch.float32, device=dev) if need_pose else None
-        check(lib.siu3r_raster_project_bwd(st.cams, V, _p(st.cams_dev), G, _p(means_c), _p(cov_c), _cov_stride(cov_c), _p(op_c), _p(shs_c), ncoef,
-                                           int(bool(ctx.sh_planar)), _p(st.rect), _p(grad), _p(g_means), _p(g_cov), _p(g_op), _p(g_sh), _p(g_m2d),
-                                           _p(part), _stream()))
+        project_bwd = lib.siu3r_raster_project_bwd_aa if st.antialiased else lib.siu3r_raster_project_bwd
+        check(project_bwd(st.cams, V, _p(st.cams_dev), G, _p(means_c), _p(cov_c), _cov_stride(cov_c), _p(op_c), _p(shs_c), ncoef,
+                          int(bool(ctx.sh_planar)), _p(st.rect), _p(grad), _p(g_means), _p(g_cov), _p(g_op), _p(g_sh), _p(g_m2d), _p(part), _stream()))
         if stats is not None:
             stats.accumulate(g_m2d if abs_m2d is None else abs_m2d, st.radii, 0.5 * V * st.W, 0.5 * V * st.H)
         g_pose = None
@@ -478,7 +493,8 @@ class _RasterizeK2(torch.autograd.Function):
         return (None, None, None, *_grads_out(ctx, 3, (g_means, g_cov, g_sh, g_op, g_pose)), g_mean2d)
 
 
-def _rasterize_views_k2(cams, means, cov6, shs, opacities, want_n_touched, entry_capacity, check_overflow, sh_planar, pose) -> Dict[str, torch.Tensor]:
+def _rasterize_views_k2(cams, means, cov6, shs, opacities, want_n_touched, entry_capacity, check_overflow, sh_planar, pose,
+                        antialiased=False) -> Dict[str, torch.Tensor]:
     def composite(st, _shs):
         V, H, W = st.V, st.H, st.W
         image, depth, alpha = _empty(st, V, 3, H, W), _empty(st, V, H, W), _empty(st, V, H, W)
@@ -487,17 +503,19 @@ def _rasterize_views_k2(cams, means, cov6, shs, opacities, want_n_touched, entry
                                                     _p(image), _p(depth), _p(alpha), _p(n_touched), _stream()))
         return dict(image=image, radii=st.radii, depth=depth, opacity=alpha, n_touched=n_touched, state=st)
 
-    return _render(cams, means, cov6, opacities, shs, shs.shape[2] if sh_planar else shs.shape[1], pose, entry_capacity, check_overflow, composite, sh_planar)
+    return _render(cams, means, cov6, opacities, shs, shs.shape[2] if sh_planar else shs.shape[1], pose, entry_capacity, check_overflow, composite, sh_planar,
+                   antialiased)
 
 
 def rasterize_k2(cam: RasterCam, means, cov6, shs, opacities, **kw) -> Dict[str, torch.Tensor]:
-    """single view: image [3,H,W], radii [G,2], depth [H,W], opacity [H,W], n_touched [G] (+ state)."""
+    """single view: image [3,H,W], radii [G,2], depth [H,W], opacity [H,W], n_touched [G] (+ state).  Keywords (antialiased among them) as
+    rasterize_views_k2."""
     o = rasterize_views_k2([cam], means, cov6, shs, opacities, **kw)
     return dict(image=o["image"][0], radii=o["radii"][0], depth=o["depth"][0], opacity=o["opacity"][0],
                 n_touched=None if o["n_touched"] is None else o["n_touched"][0], state=o["state"])
 
 
-def _contributions(cams, means, cov6, opacities, colors, channels, pose, entry_capacity, check_overflow, want_count, want_sum):
+def _contributions(cams, means, cov6, opacities, colors, channels, pose, entry_capacity, check_overflow, want_count, want_sum, antialiased=False):
     def composite(st, _chan):
         wmax = _empty(st, st.V, st.G)
         count = _empty(st, st.V, st.G, dtype=torch.int32) if want_count else None
@@ -508,11 +526,12 @@ def _contributions(cams, means, cov6, opacities, colors, channels, pose, entry_c
 
     _gpu(means, cov6, opacities)
     means, cov6, opacities = (t.detach() for t in (means, cov6, opacities))
-    return _render(cams, means, cov6, opacities, means if colors is None else colors, channels, pose, entry_capacity, check_overflow, composite)
+    return _render(cams, means, cov6, opacities, means if colors is None else colors, channels, pose, entry_capacity, check_overflow, composite,
+                   antialiased=antialiased)
 
 
 def contributions_k2(cams: Sequence[RasterCam], means, cov6, opacities, entry_capacity=None, check_overflow=True, pose_c2w=None, want_count=True,
-                     want_sum=True) -> Dict[str, torch.Tensor]:
+                     want_sum=True, antialiased=False) -> Dict[str, torch.Tensor]:
     """Blend-contribution statistics of V views of one Gaussian set, 3DGS family (siu3r_raster_contrib): with w = alpha * T the very float
     rasterize_views_k2 adds into a pixel, over the pixels of view v that blend Gaussian g -> wmax [V,G] f32 (the largest w; exactly 0 where g
     blends nowhere), count [V,G] i32 (the number of those pixels), wsum [V,G] i64 (the sum of trunc(w * 2^40): fixed point, units of 2^-40),
@@ -520,7 +539,7 @@ def contributions_k2(cams: Sequence[RasterCam], means, cov6, opacities, entry_ca
     pose_c2w as in rasterize_views_k2 (a view that overflowed an unchecked call has a NaN wmax row and zero count / wsum).  Colours take no
     part: the call projects with sh_degree = -1 on its own copy of the camera blocks and hands the projection `means` as the [G,3] colour
     operand it insists on -- no SH evaluation and no colour tensor.  No autograd: the inputs are detached.  want_count / want_sum = False
-    leave that output None."""
+    leave that output None.  antialiased=True: the weights of rasterize_views_k2(antialiased=True) (the compensated opacities)."""
     k2 = []
     for c in cams:
         c2 = RasterCam()
@@ -528,7 +547,7 @@ def contributions_k2(cams: Sequence[RasterCam], means, cov6, opacities, entry_ca
         c2.sh_degree, c2.sh_band4 = -1, 0
         k2.append(c2)
     return _contributions(k2, means, cov6, opacities, means.detach().contiguous().float(), 1, _pose(len(cams), means.device, pose_c2w=pose_c2w), entry_capacity,
-                          check_overflow, want_count, want_sum)
+                          check_overflow, want_count, want_sum, antialiased)
 
 
 def contributions_k3(cams: Sequence[RasterCam], means, cov6, opacities, entry_capacity=None, check_overflow=True, pose_dev=None, pose_c2w=None,

@@ -17,6 +17,7 @@ from .cuda_splatting import render_cuda
 from .density import FIELDS, DensityControl, DensityStats, densify_and_prune, scene_extent
 from .losses import DEPTH_MODES, DEPTH_SPACES, apply_bilagrid, apply_exposure, bilagrid_tv, depth_loss, photometric_loss
 from .mcmc import MCMCControl, event as mcmc_event, inject_noise, regularize
+from .mip import MipFilter, apply_filter3d, compute_filter3d
 from .optim import GaussianAdam, TorchAdam, log_linear, means_lr_schedule
 from .prune import ContributionPrune, gaussian_contributions, prune_by_contribution
 
@@ -123,7 +124,8 @@ def refine_gaussians(means, scales, rotations, opacities, harmonics, images, c2w
                      depth_space: str = "depth", depth_min_opacity: float = 0.5, optimizer: str = "torch", sparse: bool = False,
                      means_lr_final: Optional[float] = None, means_lr_extent_scale: bool = False,
                      sh_rest_lr_scale: float = 1.0, cameras: Optional[CameraControl] = None,
-                     prune: Optional[ContributionPrune] = None) -> Tuple[Dict[str, torch.Tensor], List[float]]:
+                     prune: Optional[ContributionPrune] = None,
+                     antialias: Optional[MipFilter] = None) -> Tuple[Dict[str, torch.Tensor], List[float]]:
     """means [G,3], scales [G,3], rotations [G,4], opacities [G], harmonics [G,3,n] (n = (deg+1)^2): what `Gaussians` carries, on the GPU.
     images [V,3,H,W]: the posed target views; c2w [V,4,4] camera-to-world, Kn [V,3,3] (or [3,3]) normalised intrinsics, near / far floats
     (or [V]), bg 3 floats: render_cuda's conventions.
@@ -214,7 +216,22 @@ def refine_gaussians(means, scales, rotations, opacities, harmonics, images, c2w
     One host read per event.  prune.final = True runs one more event after the last iteration, so the returned set is pruned.  The returned
     dict gains "prune_events": one info dict per event (prune_by_contribution's counts plus "iteration"; the final one carries `iters`).
     An event that would leave no Gaussian raises RuntimeError.  An MCMCControl keeps an exact row count and relocates its dead rows itself:
-    prune= together with it, and a schedule with every <= 0, raise ValueError before any device work."""
+    prune= together with it, and a schedule with every <= 0, raise ValueError before any device work.
+
+    antialias: a mip.MipFilter refines alias-free (Mip-Splatting, Yu et al. 2024), so that the result also holds at another image size or
+    distance; None, the default, is the loop above: nothing is launched, allocated or read that is not without the keyword, and the returned
+    bits are identical.  With antialias.filter_3d the 3-D smoothing filter (mip.compute_filter3d at the training frame size, variance
+    antialias.variance_3d) is computed from the current means and the current poses (the cameras' when a CameraControl moves them) before
+    the first render, every antialias.every iterations and after every density, MCMC or pruning event that changed or moved rows, and every
+    iteration sends exp(log-scales) and sigmoid(logit opacities) through mip.apply_filter3d before the covariance is built: the optimised
+    scales and opacities stay the raw ones, gradients reach them through the filter, the filter itself gets none.  With
+    antialias.filter_2d the render, and the contribution renders of `prune=`, run with antialiased=True (raster.rasterize_views_k2).  The
+    density rules keep looking at the raw scales, as Mip-Splatting's do.  Returned: "scales" / "opacities" stay the raw optimised ones,
+    "covariances" is what the last render would use (the filtered scales), and with filter_3d the dict gains "filter_3d" [G] in the final
+    row count; mip.bake fuses it into the fields for consumers that know nothing of it.  A control that enables neither filter, every <= 0
+    and variance_3d <= 0 raise ValueError before any device work."""
+    if antialias is not None:
+        antialias.validate()
     lambdas_depth = _check_depth_args(images, depths, depth_weights, lambda_depth, depth_mode, depth_space, depth_min_opacity, iters)
     hip = _check_optim_args(optimizer, sparse, means_lr_final, means_lr_extent_scale, sh_rest_lr_scale)
     params = tuple(params)
@@ -253,7 +270,13 @@ def refine_gaussians(means, scales, rotations, opacities, harmonics, images, c2w
     value = lambda k: _FROM_PARAM[k](free[k]) if k in free else start[k]
     cov_moves = "scales" in free or "rotations" in free
     cov6_of = lambda: raster.quat_scale_to_cov6(torch.roll(value("rotations"), 1, dims=-1), value("scales"))
-    cov6_fixed = None if cov_moves else cov6_of()
+    aa_kw = dict(antialiased=True) if antialias is not None and antialias.filter_2d else {}  # (no control: the calls carry no keyword)
+    mip3d = antialias is not None and antialias.filter_3d
+    filter3d = None  # [G], of the current rows; None: to be computed before the next render
+    if mip3d:  # the covariance is built from the filtered scales, which follow the means: nothing of it is fixed
+        cov_moves, cov6_fixed = True, None
+    else:
+        cov6_fixed = None if cov_moves else cov6_of()
 
     if lambdas_depth is not None:
         depth_target = depths.detach().float().to(dev).contiguous()
@@ -300,7 +323,7 @@ def refine_gaussians(means, scales, rotations, opacities, harmonics, images, c2w
         """one density event before iteration `it`'s render: all five fields in unconstrained form and the free ones' moments go through the
         strategy's one function (clone / split / prune, or relocate in place and grow); where it hands back new tensors they become the
         leaves and the optimiser moves to them (its step count stays); the frozen fields, cov6_fixed and the classic statistics follow"""
-        nonlocal cov6_fixed
+        nonlocal cov6_fixed, filter3d
         fields = {k: unc(k) for k in FIELDS}
         if classic:
             noise = torch.randn((strategy.stats.G, 2, 3), generator=noise_gen, device=dev, dtype=torch.float32)
@@ -316,6 +339,7 @@ def refine_gaussians(means, scales, rotations, opacities, harmonics, images, c2w
         frozen.update({k: new_p[k] for k in FIELDS if k not in free})
         start.update({k: _FROM_PARAM[k](v) for k, v in frozen.items()})
         cov6_fixed = None if cov_moves else cov6_of()
+        filter3d = None  # (rows changed or moved)
 
     def adopt(new_p, new_m):
         """the new tensors of an event become the leaves and the optimiser moves to them (its step count stays)"""
@@ -326,9 +350,10 @@ def refine_gaussians(means, scales, rotations, opacities, harmonics, images, c2w
     def prune_event(it: int):
         """one contribution-pruning event before iteration `it`'s render (after the last one: it == iters): the statistics of all training
         views under the current poses, then the row selection over all five fields and the free ones' moments, then event()'s hand-over"""
-        nonlocal cov6_fixed
-        stats = gaussian_contributions(value("means"), value("scales"), value("rotations"), value("opacities"), c2w if cam is None else cam.c2w, Kn, near_t,
-                                       far_t, (H, W))
+        nonlocal cov6_fixed, filter3d
+        sc_v, op_v = filtered()
+        stats = gaussian_contributions(value("means"), sc_v, value("rotations"), op_v, c2w if cam is None else cam.c2w, Kn, near_t,
+                                       far_t, (H, W), **aa_kw)
         fields = {k: unc(k) for k in FIELDS}
         new_p, new_m, info = prune_by_contribution(fields, stats, prune.min_weight, prune.min_views, prune.keep_at_most, opt.moments if free else None)
         if info["rows_out"] == 0:
@@ -339,8 +364,19 @@ def refine_gaussians(means, scales, rotations, opacities, harmonics, images, c2w
         frozen.update({k: new_p[k] for k in FIELDS if k not in free})
         start.update({k: _FROM_PARAM[k](v) for k, v in frozen.items()})
         cov6_fixed = None if cov_moves else cov6_of()
+        filter3d = None  # (rows left)
         if strategy.stats is not None:
             strategy.stats = DensityStats(info["rows_out"], dev, absgrad=density.absgrad)
+
+    def filtered(it: Optional[int] = None):
+        """the scales and opacities the render takes: the fields' values, or with a 3-D filter those through mip.apply_filter3d, the filter
+        recomputed first when an event dropped it or iteration `it` is one of its schedule"""
+        nonlocal filter3d
+        if not mip3d:
+            return value("scales"), value("opacities")
+        if filter3d is None or (it is not None and it % int(antialias.every) == 0):
+            filter3d = compute_filter3d(value("means"), c2w if cam is None else cam.c2w, Kn, W, H, variance=float(antialias.variance_3d))
+        return apply_filter3d(value("scales"), value("opacities"), filter3d)
 
     cam = cam_rates = None  # the cameras' state and their (lr_trans, lr_rot, lr_exposure) per iteration from cameras.start on
     grid_on = cameras is not None and exposure_mode(cameras.exposure) == "bilagrid"
@@ -367,11 +403,15 @@ def refine_gaussians(means, scales, rotations, opacities, harmonics, images, c2w
                 opt.zero_moments("opacities")
         if opt is not None:
             opt.zero_grad(set_to_none=True)
-        cov6 = cov6_of() if cov_moves else cov6_fixed
+        if mip3d:
+            scales_r, opac_r = filtered(it)
+            cov6 = raster.quat_scale_to_cov6(torch.roll(value("rotations"), 1, dims=-1), scales_r)
+        else:
+            cov6, opac_r = cov6_of() if cov_moves else cov6_fixed, None  # (None: the field's own value, formed where it always was)
         pose_holders = dict(cam_rot_delta=cam.rot_delta, cam_trans_delta=cam.trans_delta) if cam_on and cam.pose else {}
         rendered = render_cuda(cam.c2w if cam_on else c2w, Kn, near_t, far_t, (H, W), bg_t, value("means")[None].expand(V, -1, -1), cov6[None].expand(V, -1, -1),
-                               value("harmonics")[None].expand(V, -1, -1, -1), value("opacities")[None].expand(V, -1),
-                               density_stats=strategy.stats, return_aux=want_aux, **pose_holders)
+                               value("harmonics")[None].expand(V, -1, -1, -1), (value("opacities") if opac_r is None else opac_r)[None].expand(V, -1),
+                               density_stats=strategy.stats, return_aux=want_aux, **pose_holders, **aa_kw)
         img, dep = rendered[0], rendered[1]
         if cam_on and cam.exposure:
             img = apply_exposure(img, cam.M)
@@ -407,7 +447,11 @@ def refine_gaussians(means, scales, rotations, opacities, harmonics, images, c2w
         if prune is not None and prune.final and int(iters) > 0:
             prune_event(int(iters))
         out = {k: value(k).detach().clone() for k in FIELDS}
-        out["covariances"] = covariances_from(out["rotations"], out["scales"])
+        if mip3d:  # what the last render would use; the filter in the final row count (after a final pruning event: of the kept rows)
+            out["covariances"] = covariances_from(out["rotations"], filtered()[0])
+            out["filter_3d"] = filter3d.clone()
+        else:
+            out["covariances"] = covariances_from(out["rotations"], out["scales"])
         if density is not None:
             out["density_events"] = events
         if prune is not None:
