@@ -612,6 +612,25 @@ int64_t siu3r_depth_loss_ws(int V, int H, int W);
 int siu3r_depth_loss(const float* depth, const float* opacity, const float* target, const float* weight, int V, int H, int W, int mode, int space,
                      float min_opacity, float* g_depth, float* g_opacity, void* ws, float* out, float* per_view, int32_t* valid, void* stream);
 
+/* ---- instance-aware depth smoothness of splat refinement (csrc/depth_smooth.hip): value and gradient w.r.t. the K2
+ * render's depth and opacity ----
+ * depth (D = sum w z), opacity (O = sum w; may be NULL with space 0): fp32 [V,H,W]; segments: int32 [V,H,W] or NULL (one segment, nothing
+ * void), any negative id is void; all contiguous, on the device.
+ * space 0 (render): x = D, a pixel is usable iff D is finite.  space 1 (expected): x = D / O, usable iff O > min_opacity, D > 0 and both are
+ * finite (the rule of siu3r_depth_loss).  Terms along x (along y: the axes swapped): order 1: t = x[j+1] - x[j], j = 0 .. W-2; order 2:
+ * t = x[j-1] - 2 x[j] + x[j+1], j = 1 .. W-2.  A term is active iff all its pixels are usable, none is void and all carry the same id.
+ * loss = Sx / n_x + Sy / n_y, S = sum |t| over the active terms, n_x = V H (W - order), n_y = V (H - order) W: the number of term POSITIONS
+ * (inactive ones count as zeros); an axis without a position adds 0.  out = (loss, Sx / n_x, Sy / n_y, 0); per_view [V] = the view's two
+ * parts, each over the view's own positions, summed; active [V,2] int32 = the exact number of active terms per view along x and along y.
+ * g_depth, g_opacity: [V,H,W], the full derivative (sign(0) = 0), every pixel written exactly once, +0 at an unusable or void pixel; both
+ * NULL: value only.  With space 0 g_opacity may be NULL (else it is written as zeros); with space 1 they come together.
+ * ws: siu3r_depth_smooth_ws(V, H, W) BYTES of workspace, 8-byte aligned (0: the shape is not supported).  H * W < 2^31 - 1024, V <= 65535,
+ * H <= 16 * 65535, min_opacity >= 0.  Deterministic (fixed-order fp64 sums, a gather, no atomics); nothing allocates or synchronises with
+ * the host. */
+int64_t siu3r_depth_smooth_ws(int V, int H, int W);
+int siu3r_depth_smooth(const float* depth, const float* opacity, const int32_t* segments, int V, int H, int W, int order, int space,
+                       float min_opacity, float* g_depth, float* g_opacity, void* ws, float* out, float* per_view, int32_t* active, void* stream);
+
 /* ---- adaptive density control of splat refinement (csrc/density.hip; Kerbl et al. 2023, section 5.2): clone / split / prune ----
  * Deterministic (no float atomics; two calls on the same input give the same bits), nothing allocates or synchronises with the host.
  * Statistics, every iteration.  g_mean2d [V,G,2]: the pixel-space mean gradient as siu3r_raster_project_bwd writes it (rows of culled

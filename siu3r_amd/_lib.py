@@ -179,6 +179,8 @@ SIGNATURES = {
     "siu3r_photo_loss": [_P, _P, _I, _I, _I, _I, C.POINTER(C.c_int64), C.POINTER(C.c_int64), _F, _F, _P, _P, _P, _P],
     "siu3r_depth_loss_ws": [_I, _I, _I],
     "siu3r_depth_loss": [_P, _P, _P, _P, _I, _I, _I, _I, _I, _F, _P, _P, _P, _P, _P, _P, _P],
+    "siu3r_depth_smooth_ws": [_I, _I, _I],
+    "siu3r_depth_smooth": [_P, _P, _P, _I, _I, _I, _I, _I, _F, _P, _P, _P, _P, _P, _P, _P],
     "siu3r_gaussian_adam_ws": [_L],
     "siu3r_gaussian_adam": [C.POINTER(AdamField), _I, _L, C.c_double, C.c_double, _F, _F, _F, _P, _I, _I, _P, _P, _P],
     "siu3r_density_accumulate": [_P, _P, _I, _L, _F, _F, _P, _P, _P, _P],
@@ -209,6 +211,7 @@ _RESTYPES = {"siu3r_last_error": C.c_char_p, "siu3r_raster_composite_feat_ws_byt
 _RESTYPES["siu3r_photo_loss_partials"] = C.c_int64
 _RESTYPES["siu3r_density_plan_ws"] = C.c_int64
 _RESTYPES["siu3r_depth_loss_ws"] = C.c_int64
+_RESTYPES["siu3r_depth_smooth_ws"] = C.c_int64
 _RESTYPES["siu3r_gaussian_adam_ws"] = C.c_int64
 _RESTYPES["siu3r_mcmc_ws"] = C.c_int64
 _RESTYPES["siu3r_exposure_ws"] = C.c_int64

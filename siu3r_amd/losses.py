@@ -8,6 +8,8 @@ only a layout the kernel's four strides cannot express (an expanded dimension of
 
 `depth_loss` is the depth term of the same refinement (csrc/depth_loss.hip): weighted L1 or per-view Pearson correlation of the K2 render's
 depth / opacity against a target depth, value and the gradients w.r.t. both render outputs from one call.
+`depth_smoothness` is the instance-aware smoothness term on the same two maps (csrc/depth_smooth.hip): first or second differences of the
+depth, switched off across segment boundaries and at void pixels, value and both gradients from one stencil pass.
 `apply_exposure` is the per-view affine colour transform of camera optimisation (csrc/camera.hip), differentiable w.r.t. the image and M.
 `apply_bilagrid` / `bilagrid_tv` are the per-view bilateral grid of colour transforms and its total-variation regulariser (csrc/bilagrid.hip).
 There is no CPU path and nothing here synchronises with the host."""
@@ -249,6 +251,122 @@ def depth_loss(depth: torch.Tensor, opacity: torch.Tensor, target: torch.Tensor,
         out, per_view, valid, _, _ = _launch_depth(_as_vhw(depth), _as_vhw(opacity), _as_vhw(target), _as_vhw(weight), mode, space, min_opacity, False)
         loss = out[0]
     return (loss, per_view, valid) if return_terms else loss
+
+
+# ---- instance-aware depth smoothness (csrc/depth_smooth.hip) -----------------------------------------------------
+SMOOTH_ORDERS = (1, 2)
+SMOOTH_SPACES = {"render": 0, "expected": 1}
+
+
+def _check_smooth(depth, opacity, segments, order, space, min_opacity):
+    if isinstance(order, bool) or order not in SMOOTH_ORDERS:
+        raise ValueError(f"order must be one of {SMOOTH_ORDERS}, got {order!r}")
+    if space not in SMOOTH_SPACES:
+        raise ValueError(f"space must be one of {tuple(SMOOTH_SPACES)}, got {space!r}")
+    if not 0.0 <= min_opacity < float("inf"):
+        raise ValueError(f"min_opacity must be finite and >= 0, got {min_opacity}")
+    if space == "expected" and opacity is None:
+        raise ValueError('space="expected" needs the opacity map')
+    named = [("depth", depth)] + ([("opacity", opacity)] if opacity is not None else []) + ([("segments", segments)] if segments is not None else [])
+    for name, t in named:
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f"{name} must be a tensor, got {type(t).__name__}")
+    _gpu(*(t for _, t in named))
+    if depth.dim() not in (2, 3) or depth.numel() == 0:
+        raise ValueError(f"depth must be [V,H,W] or one [H,W] image, got {tuple(depth.shape)}")
+    for name, t in named:
+        if name == "segments":
+            if t.dtype == torch.bool or t.is_complex():
+                raise ValueError(f"segments must hold integer ids (any integer dtype, or a float map of whole numbers), got {t.dtype}")
+        elif t.dtype != torch.float32:
+            raise ValueError(f"the depth smoothness takes float32 maps, {name} is {t.dtype}")
+        if t.shape != depth.shape:
+            raise ValueError(f"depth {tuple(depth.shape)} and {name} {tuple(t.shape)} differ in shape")
+        if t.device != depth.device:
+            raise ValueError(f"depth is on {depth.device}, {name} on {t.device}")
+
+
+def _launch_smooth(depth3, opacity3, segments3, order: int, space: str, min_opacity: float, want_grad: bool):
+    """One siu3r_depth_smooth call on contiguous [V,H,W] maps (segments3: int32 or None).  Returns (out [4] = loss, x-axis part, y-axis
+    part, 0; per_view [V]; active [V,2] int32; g_depth, g_opacity or None; g_opacity is None in the render space)."""
+    lib = _lib.lib()
+    V, H, W = depth3.shape
+    dev = depth3.device
+    nbytes = int(lib.siu3r_depth_smooth_ws(V, H, W))
+    if nbytes <= 0:
+        raise ValueError(f"depth maps {tuple(depth3.shape)} are too large for the depth smoothness kernel")
+    ws = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+    out = torch.empty(4, dtype=torch.float32, device=dev)
+    per_view = torch.empty(V, dtype=torch.float32, device=dev)
+    active = torch.empty((V, 2), dtype=torch.int32, device=dev)
+    expected = SMOOTH_SPACES[space] == 1
+    gd = torch.empty_like(depth3) if want_grad else None
+    go = torch.empty_like(depth3) if want_grad and expected else None
+    with torch.cuda.device(dev):
+        check(lib.siu3r_depth_smooth(_p(depth3), _p(opacity3) if expected else None, _p(segments3), V, H, W, int(order), SMOOTH_SPACES[space],
+                                     float(min_opacity), _p(gd), _p(go), _p(ws), _p(out), _p(per_view), _p(active), _stream()))
+    return out, per_view, active, gd, go
+
+
+def _segments_i32(segments: Optional[torch.Tensor]) -> Optional[torch.Tensor]:
+    """contiguous int32 [V,H,W] ids of a [V,H,W] / [H,W] map of any integer dtype or of whole-number floats (one conversion at the most)"""
+    if segments is None:
+        return None
+    s = segments.detach()
+    return (s.unsqueeze(0) if s.dim() == 2 else s).to(torch.int32).contiguous()
+
+
+class _DepthSmooth(torch.autograd.Function):
+    """The fused kernel: the forward call already produces d loss / d depth and d loss / d opacity for a loss gradient of 1, the backward
+    is one multiply per needed map."""
+
+    @staticmethod
+    def forward(ctx, depth, opacity, segments3, order, space, min_opacity):
+        out, per_view, active, gd, go = _launch_smooth(_as_vhw(depth), _as_vhw(opacity), segments3, order, space, min_opacity, True)
+        ctx.save_for_backward(gd, go if ctx.needs_input_grad[1] else None)  # (an opacity map nobody differentiates is not kept)
+        ctx.shape = depth.shape
+        ctx.mark_non_differentiable(per_view, active)
+        return out[0], per_view, active
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g_loss, _g_per_view, _g_active):
+        gd, go = ctx.saved_tensors
+        g_depth = (gd * g_loss).reshape(ctx.shape) if ctx.needs_input_grad[0] else None
+        g_opacity = None
+        if ctx.needs_input_grad[1]:  # (the render space does not read the opacity: its derivative is zero)
+            g_opacity = (go * g_loss).reshape(ctx.shape) if go is not None else torch.zeros(ctx.shape, dtype=gd.dtype, device=gd.device)
+        return g_depth, g_opacity, None, None, None, None
+
+
+def depth_smoothness(depth: torch.Tensor, opacity: Optional[torch.Tensor] = None, segments: Optional[torch.Tensor] = None, order: int = 1,
+                     space: str = "render", min_opacity: float = 0.5, return_terms: bool = False):
+    """Instance-aware depth smoothness on the K2 render's own outputs, as a 0-d device tensor: `depth` is the render's sum w z, `opacity`
+    its sum w (needed only for space="expected"), both float32 [V,H,W] (or one [H,W] image) on the GPU; `segments` holds a segment id per
+    pixel in the same shape (any integer dtype, or a float map of whole numbers such as the all -1.0 map of an empty panoptic result; it is
+    converted to int32 once), any negative id is void; None is one segment with nothing void: plain, ungated smoothness.
+
+    space="render" smooths x = depth (the form of the SIU3R training objective), a pixel is usable iff depth is finite; space="expected"
+    smooths x = depth / opacity, usable iff opacity > min_opacity, depth > 0 and both are finite (depth_loss's rule).  order=1 takes the
+    forward differences x[j+1] - x[j] along both image axes, order=2 the second differences x[j-1] - 2 x[j] + x[j+1], which leave a slanted
+    plane alone.  A difference counts iff all its pixels are usable, none is void and all carry the same segment id: depth may jump between
+    segments and is pulled flat (order 1) or planar (order 2) inside one.  The loss is the sum over the two axes of sum |difference| /
+    number of difference positions of that axis over all views (V H (W - order) and V (H - order) W; gated positions count as zeros, as
+    in the training objective); an axis too short to have a position adds 0 (where the training objective would give NaN).
+
+    Differentiable w.r.t. `depth` and `opacity` (the subgradient of |x| at 0 is 0; an unusable or void pixel receives a zero gradient);
+    `segments` receives none.  return_terms: (loss, per_view [V], active [V,2] int32), the last two detached: per view the same loss over
+    the view's own positions, and the exact number of counted differences along x and along y.  Non-contiguous inputs cost a
+    `.contiguous()`.  Deterministic; there is no CPU path, and nothing here synchronises with the host."""
+    min_opacity = float(min_opacity)
+    _check_smooth(depth, opacity, segments, order, space, min_opacity)
+    seg3 = _segments_i32(segments)
+    if torch.is_grad_enabled() and (depth.requires_grad or (opacity is not None and opacity.requires_grad)):
+        loss, per_view, active = _DepthSmooth.apply(depth, opacity, seg3, order, space, min_opacity)
+    else:
+        out, per_view, active, _, _ = _launch_smooth(_as_vhw(depth), _as_vhw(opacity), seg3, order, space, min_opacity, False)
+        loss = out[0]
+    return (loss, per_view, active) if return_terms else loss
 
 
 # ---- per-view exposure (csrc/camera.hip, DESIGN.md section 21) -------------------------------------------------------------------------

@@ -15,11 +15,12 @@ from . import raster
 from .cameras import CameraControl, CameraState, exposure_mode, identity_grids
 from .cuda_splatting import render_cuda
 from .density import FIELDS, DensityControl, DensityStats, densify_and_prune, scene_extent
-from .losses import DEPTH_MODES, DEPTH_SPACES, apply_bilagrid, apply_exposure, bilagrid_tv, depth_loss, photometric_loss
+from .losses import DEPTH_MODES, DEPTH_SPACES, apply_bilagrid, apply_exposure, bilagrid_tv, depth_loss, depth_smoothness, photometric_loss
 from .mcmc import MCMCControl, event as mcmc_event, inject_noise, regularize
 from .mip import MipFilter, apply_filter3d, compute_filter3d
 from .optim import GaussianAdam, TorchAdam, log_linear, means_lr_schedule
 from .prune import ContributionPrune, gaussian_contributions, prune_by_contribution
+from .smooth import DepthSmoothness
 
 # Adam steps per field, those of the 3DGS training recipe (Kerbl et al. 2023): position 1.6e-4, scaling 5e-3, rotation 1e-3, opacity 5e-2,
 # SH 2.5e-3.  The recipe also multiplies the position rate by the scene extent and decays it, and steps the higher SH bands at a twentieth:
@@ -83,6 +84,24 @@ def _check_depth_args(images, depths, depth_weights, lambda_depth, depth_mode, d
     return None if off else schedule
 
 
+def _check_smooth_args(images, smooth, segments, iters) -> Optional[List[float]]:
+    """host-side validation of refine_gaussians' smoothness keywords, before any device work; the schedule, or None without a control"""
+    if smooth is None:
+        if segments is not None:
+            raise ValueError("segments without a `smooth` control: pass smooth=DepthSmoothness(...)")
+        return None
+    if not isinstance(smooth, DepthSmoothness):
+        raise ValueError(f"smooth must be a smooth.DepthSmoothness or None, got {type(smooth).__name__}")
+    smooth.validate()
+    if segments is not None:
+        want = (images.shape[0], images.shape[-2], images.shape[-1])
+        if not isinstance(segments, torch.Tensor) or tuple(segments.shape) != want:
+            raise ValueError(f"segments must be a [V,H,W] tensor matching images: expected {want}, got {tuple(getattr(segments, 'shape', ()))}")
+        if segments.dtype == torch.bool or segments.is_complex():
+            raise ValueError(f"segments must hold integer ids, got {segments.dtype}")
+    return smooth.weights(iters)
+
+
 OPTIMIZERS = ("torch", "hip")
 
 
@@ -125,7 +144,8 @@ def refine_gaussians(means, scales, rotations, opacities, harmonics, images, c2w
                      means_lr_final: Optional[float] = None, means_lr_extent_scale: bool = False,
                      sh_rest_lr_scale: float = 1.0, cameras: Optional[CameraControl] = None,
                      prune: Optional[ContributionPrune] = None,
-                     antialias: Optional[MipFilter] = None) -> Tuple[Dict[str, torch.Tensor], List[float]]:
+                     antialias: Optional[MipFilter] = None, smooth: Optional[DepthSmoothness] = None,
+                     segments=None) -> Tuple[Dict[str, torch.Tensor], List[float]]:
     """means [G,3], scales [G,3], rotations [G,4], opacities [G], harmonics [G,3,n] (n = (deg+1)^2): what `Gaussians` carries, on the GPU.
     images [V,3,H,W]: the posed target views; c2w [V,4,4] camera-to-world, Kn [V,3,3] (or [3,3]) normalised intrinsics, near / far floats
     (or [V]), bg 3 floats: render_cuda's conventions.
@@ -229,9 +249,22 @@ def refine_gaussians(means, scales, rotations, opacities, harmonics, images, c2w
     density rules keep looking at the raw scales, as Mip-Splatting's do.  Returned: "scales" / "opacities" stay the raw optimised ones,
     "covariances" is what the last render would use (the filtered scales), and with filter_3d the dict gains "filter_3d" [G] in the final
     row count; mip.bake fuses it into the fields for consumers that know nothing of it.  A control that enables neither filter, every <= 0
-    and variance_3d <= 0 raise ValueError before any device work."""
+    and variance_3d <= 0 raise ValueError before any device work.
+
+    smooth: a smooth.DepthSmoothness adds the instance-aware depth smoothness of the SIU3R training objective; None, the default, is the loop
+    above: depth_smoothness is never called, nothing is launched, allocated or read that is not without the keyword, and no new keyword
+    reaches render_cuda.  With a control the objective of iteration t gains weight_t * losses.depth_smoothness(render depth, render
+    opacity, segments, smooth.order, smooth.space, smooth.min_opacity) on the same render (space="expected" asks the render for its
+    opacity map, as the depth term does); smooth.weight is a float or a (start, end) pair decayed exponentially over the iterations
+    (depth_weight_schedule).  segments [V,H,W] are the segment ids of the TRAINING views (any integer dtype, negative = void: the
+    `segmentation` SIU3RModel.forward returns for its context views); they are converted to int32 once and stay fixed.  segments=None with
+    a control is plain, ungated smoothness.  `losses` then logs the total objective and the returned dict gains "smooth_losses": the
+    unweighted term at the logged iterations.  `density=`, `depths=`, `cameras=`, `prune=`, `antialias=` and optimizer="hip" work
+    unchanged; the density statistics see the gradient of the total objective.  segments without a control, segments of another shape
+    than the views, a weight that is not positive and finite and an unknown order or space raise ValueError before any device work."""
     if antialias is not None:
         antialias.validate()
+    lambdas_smooth = _check_smooth_args(images, smooth, segments, iters)
     lambdas_depth = _check_depth_args(images, depths, depth_weights, lambda_depth, depth_mode, depth_space, depth_min_opacity, iters)
     hip = _check_optim_args(optimizer, sparse, means_lr_final, means_lr_extent_scale, sh_rest_lr_scale)
     params = tuple(params)
@@ -281,9 +314,13 @@ def refine_gaussians(means, scales, rotations, opacities, harmonics, images, c2w
     if lambdas_depth is not None:
         depth_target = depths.detach().float().to(dev).contiguous()
         depth_conf = None if depth_weights is None else depth_weights.detach().float().to(dev).contiguous()
-    want_aux = lambdas_depth is not None or bool(sparse)  # (it selects want_n_touched: off for the plain path)
+    smooth_opacity = lambdas_smooth is not None and smooth.space == "expected"  # (the render space reads the depth map alone)
+    if lambdas_smooth is not None:
+        segment_ids = None if segments is None else segments.detach().to(dev).to(torch.int32).contiguous()
+    want_aux = lambdas_depth is not None or bool(sparse) or smooth_opacity  # (it selects want_n_touched: off for the plain path)
     losses: List[float] = []
     depth_losses: List[float] = []
+    smooth_losses: List[float] = []
     events: List[dict] = []
     prune_events: List[dict] = []
     classic = density is not None and not budgeted
@@ -417,13 +454,16 @@ def refine_gaussians(means, scales, rotations, opacities, harmonics, images, c2w
             img = apply_exposure(img, cam.M)
         elif cam_on and grid_on:
             img = apply_bilagrid(img, cam.grids)
-        opa = _aux_cat(rendered[2], "opacity") if lambdas_depth is not None else None
+        opa = _aux_cat(rendered[2], "opacity") if lambdas_depth is not None or smooth_opacity else None
         radii = _aux_cat(rendered[2], "radii") if sparse else None
         if lambdas_depth is None:
             loss = photometric_loss(img, target, lambda_dssim)
         else:
             d_loss = depth_loss(dep, opa, depth_target, depth_conf, depth_mode, depth_space, depth_min_opacity)
             loss = photometric_loss(img, target, lambda_dssim) + lambdas_depth[it] * d_loss
+        if lambdas_smooth is not None:
+            s_loss = depth_smoothness(dep, opa if smooth_opacity else None, segment_ids, smooth.order, smooth.space, smooth.min_opacity)
+            loss = loss + lambdas_smooth[it] * s_loss
         if cam_on and grid_on and float(cameras.lambda_tv) > 0.0:
             loss = loss + float(cameras.lambda_tv) * bilagrid_tv(cam.grids)
         loss.backward()
@@ -443,6 +483,8 @@ def refine_gaussians(means, scales, rotations, opacities, harmonics, images, c2w
             losses.append(float(loss.detach()))
             if lambdas_depth is not None:
                 depth_losses.append(float(d_loss.detach()))
+            if lambdas_smooth is not None:
+                smooth_losses.append(float(s_loss.detach()))
     with torch.no_grad():
         if prune is not None and prune.final and int(iters) > 0:
             prune_event(int(iters))
@@ -458,6 +500,8 @@ def refine_gaussians(means, scales, rotations, opacities, harmonics, images, c2w
             out["prune_events"] = prune_events
         if lambdas_depth is not None:
             out["depth_losses"] = depth_losses
+        if lambdas_smooth is not None:
+            out["smooth_losses"] = smooth_losses
         if hip:
             out["optimizer_steps"] = opt.step_count if free else 0
         if cameras is not None:
