@@ -291,6 +291,20 @@ int siu3r_stem7x7_x3(const float* img, const void* wfrag, const float* bias, con
  * Instantiations: K = 256 with 65 <= N <= 96, K = 128 with N <= 32.  Same bf16x3 products as siu3r_gemm, another K order. */
 int siu3r_proj_rows_x3(const float* x, const void* wfrag, const float* bias, float* out, int Z, int G, int64_t M, int K, int N, int ldc,
                        int64_t out_z_stride, void* stream);
+/* The row chain that ends a Mask2Former pixel-decoder encoder layer (reference video_seg_decoder.py:945-1018) as one launch, bf16x3,
+ * d_model = 256, for rows [0, M) of contiguous [M, 256] fp32 tensors:
+ *   y = x Wo^T + bo + res;  z = LN(y; g1, b1, eps1);  h = relu(z W1^T + c1);  o = h W2^T + c2 + z;  out = LN(o; g2, b2, eps2)
+ * with Wo [256, 256], W1 [H, 256], W2 [256, H], H a multiple of 256 (the hidden layer is produced and consumed on chip in 256-column
+ * chunks).  Every product is A_hi W_hi + A_lo W_hi + A_hi W_lo with fp32 accumulation, A split as siu3r_gemm splits it (hi = the upper
+ * 16 bits, lo = bf16(a - hi)), K ascending in steps of 16 and per step hi x hi, hi x lo, lo x hi, then bias, activation, residual: the
+ * order of siu3r_gemm's ping-pong kernels, so that on shapes those kernels serve the result equals the five separate launches bit for
+ * bit; the LayerNorms are siu3r_layernorm's (fp32, the mean first, then the centred sum of squares; the same sums at C = 256).
+ * pack (siu3r_amd/ops.py pack_rowchain): the fragments of Wo, W1, W2 in siu3r_proj_rows_x3's layout, one after the other, then fp32
+ * bo, g1, b1, c2, g2, b2 [256 each] and c1 [H].  No atomics: two launches on the same inputs give the same bits.
+ * REFUSED before anything is launched (non-zero return, siu3r_last_error, nothing written): a null pointer, M <= 0 (an empty M is
+ * refused as siu3r_proj_rows_x3 refuses it: the caller skips the call), H that is not a positive multiple of 256, a base pointer that
+ * is not 16-byte aligned.  out may NOT alias x or res: a workgroup's rows are read and written at different times. */
+int siu3r_rowchain_x3(const float* x, const float* res, const void* pack, float* out, int64_t M, int H, float eps1, float eps2, void* stream);
 /* depth-wise 3x3 + bias + GELU over the 3 token scales of the adapter ConvFFN (vit_adapter.py:16-59) */
 int siu3r_dwconv3x3_gelu(const void* x, void* y, int dtype, const float* w9c, const float* bias, int B, int H,
                          int W, int C, void* stream);

@@ -102,6 +102,19 @@ class _Weights:
             self.lin[key] = ops.pack_proj([self.t(n + ".weight") for n in names], [self.t(n + ".bias") if (n + ".bias") in self.sd else None for n in names])
         return self.lin[key]
 
+    def rowchain(self, p):
+        """the row chain that ends the pixel-decoder encoder layer `p` (output_proj, self_attn_layer_norm, fc1, fc2, final_layer_norm) as
+        the pack of siu3r_rowchain_x3 -> (pack, H)"""
+        key = "rowchain:" + p
+        if key not in self.lin:
+            t = self.t
+            self.lin[key] = (ops.pack_rowchain(t(p + ".self_attn.output_proj.weight"), t(p + ".self_attn.output_proj.bias"),
+                                               t(p + ".self_attn_layer_norm.weight"), t(p + ".self_attn_layer_norm.bias"),
+                                               t(p + ".fc1.weight"), t(p + ".fc1.bias"), t(p + ".fc2.weight"), t(p + ".fc2.bias"),
+                                               t(p + ".final_layer_norm.weight"), t(p + ".final_layer_norm.bias")),
+                             self.sd[p + ".fc1.weight"].shape[0])
+        return self.lin[key]
+
     def merged(self, key, names):
         if key not in self.lin:
             w = torch.cat([self.t(n + ".weight") for n in names], 0)
@@ -941,6 +954,9 @@ def _sine_pos_3d(t, h, w, npf=128):
     return (torch.cat((f(py), f(px)), dim=3) + f(pz)).reshape(t * h * w, 2 * npf)
 
 
+_ROWCHAIN = os.environ.get("SIU3R_NO_ROWCHAIN", "0") != "1"  # A/B switch: output_proj, LN, fc1, fc2, LN of a pixel-decoder layer as five launches again
+
+
 class VideoMask2FormerForVideoSegmentationOutput(dict):
     """Attribute-style output like the reference's ModelOutput (video_seg_decoder.py:2464-2471)."""
 
@@ -1006,6 +1022,10 @@ class VideoMask2FormerForVideoSegmentation:
             offs_aw = ops.linear(hsb, ctx.w.lin[wkey], out_dtype=torch.float32, residual=pres if N2 == 1 else pres[None].expand(N2, -1, -1))
             value = ops.linear(hsb, ctx.w.linear(p + ".self_attn.value_proj"), out_dtype=ctx.act)
             samp = ops.msdeform_sample(value, offs_aw, ref, shapes, 8, 4, ctx.act)
+            if _ROWCHAIN and ops.rowchain_ok(samp, hs, ctx.split):  # the layer's five row-local launches as one
+                pack, H = ctx.w.rowchain(p)
+                hs = hsb = ops.rowchain_x3(samp, hs, pack, H, 1e-5, 1e-5)
+                continue
             a = ops.linear(samp, ctx.w.linear(p + ".self_attn.output_proj"), out_dtype=torch.float32, residual=hs)
             hs, hsb = ctx.ln2(p + ".self_attn_layer_norm", a, 1e-5)
             f_ = ops.linear(hsb, ctx.w.linear(p + ".fc1"), out_dtype=ctx.act, act=ACT_RELU)

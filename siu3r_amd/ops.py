@@ -858,6 +858,20 @@ def stem7x7_x3(img: torch.Tensor, wfrag: torch.Tensor, bias: Optional[torch.Tens
     return out
 
 
+def _proj_fragments(w: torch.Tensor) -> torch.Tensor:
+    """one matrix [N, K] as the fragments of pack_proj: bf16 [NB, K/16, 2, 64, 8]"""
+    w = w.detach().float().reshape(w.shape[0], -1)
+    N, K = w.shape
+    NB = (N + 31) // 32
+    assert K % 16 == 0
+    wp = torch.zeros((NB * 32, K), dtype=torch.float32, device=w.device)
+    wp[:N] = w
+    fr = wp.reshape(NB, 32, K // 16, 2, 8).permute(0, 2, 3, 1, 4).reshape(NB, K // 16, 64, 8)  # [nb, s, lane = 32 chunk + n % 32, j]
+    hi = fr.to(torch.bfloat16)
+    lo = (fr - hi.float()).to(torch.bfloat16)
+    return torch.stack([hi, lo], dim=2)
+
+
 def pack_proj(weights: Sequence[torch.Tensor], biases: Sequence[Optional[torch.Tensor]]):
     """MFMA B fragments of G projection matrices [N, K] (a 1 x 1 convolution's [N, K, 1, 1] is reshaped) for siu3r_proj_rows_x3 ->
     (bf16 [G, NB, K/16, 2, 64, 8], fp32 bias [G, 32 NB] or None, N).  Fragment of (column block nb, K step s): lane l holds column
@@ -865,16 +879,8 @@ def pack_proj(weights: Sequence[torch.Tensor], biases: Sequence[Optional[torch.T
     frs, N = [], None
     for w in weights:
         _gpu(w)
-        w = w.detach().float().reshape(w.shape[0], -1)
-        N, K = w.shape
-        NB = (N + 31) // 32
-        assert K % 16 == 0
-        wp = torch.zeros((NB * 32, K), dtype=torch.float32, device=w.device)
-        wp[:N] = w
-        fr = wp.reshape(NB, 32, K // 16, 2, 8).permute(0, 2, 3, 1, 4).reshape(NB, K // 16, 64, 8)  # [nb, s, lane = 32 chunk + n % 32, j]
-        hi = fr.to(torch.bfloat16)
-        lo = (fr - hi.float()).to(torch.bfloat16)
-        frs.append(torch.stack([hi, lo], dim=2))
+        N = w.shape[0]
+        frs.append(_proj_fragments(w))
     b = None
     if any(x is not None for x in biases):
         NB = frs[0].shape[0]
@@ -900,6 +906,55 @@ def proj_rows_x3(x: torch.Tensor, wfrag: torch.Tensor, bias: Optional[torch.Tens
 
 def proj_rows_ok(K: int, n: int) -> bool:
     return (K == 256 and 65 <= n <= 96) or (K == 128 and n <= 32)
+
+
+def pack_rowchain(wo, bo, g1, b1, w1, c1, w2, c2, g2, b2) -> torch.Tensor:
+    """The weights of siu3r_rowchain_x3 as one uint8 buffer: the fragments of Wo [256, 256], W1 [H, 256] and W2 [256, H] in pack_proj's layout
+    (planes hi = bf16(w), lo = bf16(w - hi)), one after the other, then fp32 bo, g1, b1, c2, g2, b2 [256 each] and c1 [H]."""
+    H = w1.shape[0]
+    assert tuple(wo.shape) == (256, 256) and tuple(w1.shape) == (H, 256) and tuple(w2.shape) == (256, H) and H > 0 and H % 256 == 0
+    vec = [bo, g1, b1, c2, g2, b2, c1]
+    assert all(v.numel() == (H if v is c1 else 256) for v in vec)
+    parts = [_proj_fragments(w).contiguous().view(torch.uint8).reshape(-1) for w in (wo, w1, w2)]
+    parts.append(torch.cat([v.detach().float().reshape(-1) for v in vec]).contiguous().view(torch.uint8))
+    return torch.cat(parts).contiguous()
+
+
+def unpack_rowchain(pack: torch.Tensor, H: int) -> dict:
+    """pack_rowchain read back: the matrices as float64 hi + lo (what the kernel multiplies) and the fp32 vectors"""
+    def mat(buf, N, K):
+        fr = buf.view(torch.bfloat16).reshape(N // 32, K // 16, 2, 2, 32, 8).double()   # [nb, s, plane, chunk, n % 32, j]
+        return (fr[:, :, 0] + fr[:, :, 1]).permute(0, 3, 1, 2, 4).reshape(N, K)          # [nb, n % 32, s, chunk, j]
+    pack = pack.cpu()
+    o1, o2, o3 = 256 * 256 * 4, 256 * 256 * 4 + H * 256 * 4, 256 * 256 * 4 + 2 * H * 256 * 4
+    assert pack.dtype == torch.uint8 and pack.numel() == o3 + (6 * 256 + H) * 4
+    vec = pack[o3:].view(torch.float32)
+    out = {"wo": mat(pack[:o1], 256, 256), "w1": mat(pack[o1:o2], H, 256), "w2": mat(pack[o2:o3], 256, H)}
+    for i, k in enumerate(("bo", "g1", "b1", "c2", "g2", "b2")):
+        out[k] = vec[256 * i:256 * (i + 1)].clone()
+    out["c1"] = vec[6 * 256:].clone()
+    return out
+
+
+def rowchain_ok(x: torch.Tensor, res: torch.Tensor, split: bool) -> bool:
+    """siu3r_rowchain_x3 serves bf16x3 only, on contiguous fp32 rows of 256 columns"""
+    return bool(split) and all(t.dtype == torch.float32 and t.is_contiguous() and t.dim() >= 2 and t.shape[-1] == 256 for t in (x, res)) \
+        and x.shape == res.shape
+
+
+def rowchain_x3(x: torch.Tensor, res: torch.Tensor, pack: torch.Tensor, H: int, eps1: float, eps2: float, out: Optional[torch.Tensor] = None):
+    """out = LN(h W2^T + c2 + z), h = relu(z W1^T + c1), z = LN(x Wo^T + bo + res): the five row-local launches that end a pixel-decoder
+    encoder layer as one (siu3r_rowchain_x3).  x, res [..., 256] fp32 contiguous; out must not alias them."""
+    _gpu(x, res, pack, out)
+    assert rowchain_ok(x, res, True), (x.shape, x.dtype, res.shape, res.dtype)
+    assert pack.dtype == torch.uint8 and pack.numel() == (256 * 256 + 2 * H * 256) * 4 + (6 * 256 + H) * 4
+    if out is None:
+        out = torch.empty_like(x)
+    assert out.shape == x.shape and out.dtype == torch.float32 and out.is_contiguous()
+    M = x.numel() // 256
+    if M:
+        check(_lib.lib().siu3r_rowchain_x3(_p(x), _p(res), _p(pack), _p(out), M, H, eps1, eps2, _stream()))
+    return out
 
 
 def image_channels(split: bool) -> int:
