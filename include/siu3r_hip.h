@@ -26,7 +26,7 @@ extern "C" {
 #define SIU3R_F64 3
 
 const char* siu3r_last_error(void);
-#define SIU3R_ABI_VERSION 12 /* 12: siu3r_gemm_plan_t.skinny_path (which code multiplies the remainder rows); 11: siu3r_attention_plan (what siu3r_attention launches for a parameter block); 10: siu3r_stem7x7_x3 (the Gaussian heads' stem as one dedicated kernel), siu3r_proj_rows_x3 (the heads' last 1 x 1 convolutions as row streams); 9: siu3r_raster_project_c2w + siu3r_raster_cam.k2_near / k2_far (the reference renderer's own pose tensors, consumed on the device), siu3r_raster_tune (replaces the SIU3R_FEAT_FORM / SIU3R_FEAT_NP environment switches; the shared-batch matrix-core composite is gone: no workspace = 32-channel kernel); 8: LPIPS (siu3r_maxpool2x2s2, siu3r_lpips_layer); 7: device-side poses for the gsplat seam (siu3r_raster_project_dp, siu3r_sh_eval_dp, siu3r_blend_background_dp), precomputed K2 colours (sh_degree < 0), all-channel list composite; 6: pre-split bf16x3 activations (siu3r_gemm_params.c_x3 / a_x3, siu3r_gemm_plan_t.a_x3_ok / c_x3_ok), siu3r_attn_params.kv_bxor / kv_x3, siu3r_gemm_params.c_x3_col0; 5: siu3r_raster_sort takes stage 1's counters (culled Gaussians leave the sort), NaN-poisoned views on entry overflow, siu3r_gemm_tune key 4; 4: siu3r_gemm_plan, split-K workspace capacities + self-resetting tickets, tile_cfg; 3: view-batched sort-free rasterizer */
+#define SIU3R_ABI_VERSION 13 /* 13: siu3r_panoptic_stage1 takes the overlap threshold as a double (the reference compares the float32 area ratio with the double 0.8: a ratio that rounds to fp32(0.8) is accepted); 12: siu3r_gemm_plan_t.skinny_path (which code multiplies the remainder rows); 11: siu3r_attention_plan (what siu3r_attention launches for a parameter block); 10: siu3r_stem7x7_x3 (the Gaussian heads' stem as one dedicated kernel), siu3r_proj_rows_x3 (the heads' last 1 x 1 convolutions as row streams); 9: siu3r_raster_project_c2w + siu3r_raster_cam.k2_near / k2_far (the reference renderer's own pose tensors, consumed on the device), siu3r_raster_tune (replaces the SIU3R_FEAT_FORM / SIU3R_FEAT_NP environment switches; the shared-batch matrix-core composite is gone: no workspace = 32-channel kernel); 8: LPIPS (siu3r_maxpool2x2s2, siu3r_lpips_layer); 7: device-side poses for the gsplat seam (siu3r_raster_project_dp, siu3r_sh_eval_dp, siu3r_blend_background_dp), precomputed K2 colours (sh_degree < 0), all-channel list composite; 6: pre-split bf16x3 activations (siu3r_gemm_params.c_x3 / a_x3, siu3r_gemm_plan_t.a_x3_ok / c_x3_ok), siu3r_attn_params.kv_bxor / kv_x3, siu3r_gemm_params.c_x3_col0; 5: siu3r_raster_sort takes stage 1's counters (culled Gaussians leave the sort), NaN-poisoned views on entry overflow, siu3r_gemm_tune key 4; 4: siu3r_gemm_plan, split-K workspace capacities + self-resetting tickets, tile_cfg; 3: view-batched sort-free rasterizer */
 int siu3r_abi_version(void);
 
 /* ---- seam 1: curope.rope_2d(tokens, positions, base, fwd)
@@ -564,13 +564,15 @@ int siu3r_split_bf16(const float* x, void* hi, void* lo, void* x3, int64_t rows,
  * class_logits [B,Q,C] fp32; mask_logits_cl [B,T,IH,IW,Q] fp32 (channel-last).  All other pointers are outputs /
  * workspaces: probs [B,Q,C], scores [B,Q], labels/kept_idx [B,Q] i32, n_keep [B] i32, p256 [B,T,Q,ms,ms] fp32 (the ms x ms probability planes of the KEPT queries of an item: plane k < n_keep[b] belongs to query kept_idx[b,k]; the rest is not written),
  * lab_map [B,T,H,W] i32, area/orig [B,Q] i32, per-kept-query table seg_id/seg_label/seg_fused [B,Q] i32 + seg_score
- * [B,Q] fp32, acc_list [B,Q] / n_acc [B] i32, and the maps seg/sem/ins [B,T,H,W] i32.  fuse_mask bit c = class c fuses. */
+ * [B,Q] fp32, acc_list [B,Q] / n_acc [B] i32, and the maps seg/sem/ins [B,T,H,W] i32.  fuse_mask bit c = class c fuses.
+ * threshold and mask_threshold are compared in float32 (as torch compares a float32 tensor with a Python scalar); overlap is a DOUBLE: the
+ * float32 quotient area / orig is widened and compared with it, as the reference compares `ratio.item()` with its Python float. */
 int siu3r_panoptic_stage1(const float* class_logits, const float* mask_logits_cl, float* probs, float* scores,
                           int32_t* labels, int32_t* kept_idx, int32_t* n_keep, float* p256, int32_t* lab_map,
                           int32_t* area, int32_t* orig, int32_t* seg_id, int32_t* seg_label, int32_t* seg_fused,
                           float* seg_score, int32_t* acc_list, int32_t* n_acc, int32_t* seg, int32_t* sem, int32_t* ins,
                           int B, int T, int Q, int C, int IH, int IW, int H, int W, int mask_size, float threshold,
-                          float mask_threshold, float overlap, uint32_t fuse_mask, void* stream);
+                          float mask_threshold, double overlap, uint32_t fuse_mask, void* stream);
 /* query_class_logits of batch item b in Gaussian-major layout out[(t,y,x), j, c] (model.py:261-263) */
 int siu3r_panoptic_qcl(const float* p256, const float* probs, const int32_t* kept_idx, const int32_t* acc_list, int nq,
                        float* out, int b, int T, int H, int W, int mask_size, int Q, int C, void* stream);

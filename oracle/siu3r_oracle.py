@@ -630,14 +630,15 @@ def m2f_decoder(w: W, ms: Sequence[T], mask_features: T, B: int, Tn: int, heads:
 # panoptic post-process (image_processing_video_mask2former.py:1238-1481)
 # ----------------------------------------------------------------------------------------
 def panoptic_postprocess(class_logits: T, mask_logits: T, target_hw, threshold=0.5, mask_threshold=0.5,
-                         overlap=0.8, fuse=(0, 1)):
+                         overlap=0.8, fuse=(0, 1), mask_size=256):
     """Returns list (per batch item) of dict(segmentation, segments_info, query_class_logits, query_scores).
-    Reproduces the hard-coded (256,256) intermediate size (:1298), the empty branch returning a float
+    Reproduces the hard-coded (256,256) intermediate size (:1298; `mask_size` exists for the stage tests, which run the same
+    restatement at smaller intermediate sizes), the empty branch returning a float
     map of -1 (:1351-1375) and the 'height,width' rebinding quirk of the no-accepted-query branch (:1468-1472)."""
     Bn, Q, Tn, height, width = mask_logits.shape
     num_labels = class_logits.shape[-1] - 1
     ml = mask_logits.permute(0, 2, 1, 3, 4).reshape(Bn * Tn, Q, height, width)
-    ml = F.interpolate(ml, size=(256, 256), mode="bilinear", align_corners=False).view(Bn, Tn, Q, 256, 256)
+    ml = F.interpolate(ml, size=(mask_size, mask_size), mode="bilinear", align_corners=False).view(Bn, Tn, Q, mask_size, mask_size)
     mask_probs = ml.sigmoid()
     class_probs = class_logits.softmax(-1)
     scores, labels = class_probs.max(-1)

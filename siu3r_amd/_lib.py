@@ -100,7 +100,7 @@ class AdamField(C.Structure):
 
 # name -> argtypes; restype is c_int unless listed in _RESTYPES.  Mirrors include/siu3r_hip.h.
 _P, _I, _L, _F = C.c_void_p, C.c_int, C.c_int64, C.c_float
-ABI_VERSION = 12  # SIU3R_ABI_VERSION of include/siu3r_hip.h these ctypes declarations mirror
+ABI_VERSION = 13  # SIU3R_ABI_VERSION of include/siu3r_hip.h these ctypes declarations mirror
 
 SIGNATURES = {
     "siu3r_last_error": [],
@@ -205,7 +205,7 @@ SIGNATURES = {
     "siu3r_bilagrid_tv_ws": [_I, _I, _I, _I],
     "siu3r_bilagrid_tv": [_P, _I, _I, _I, _I, _F, _P, _P, _P, _P],
     "siu3r_lift_ids":[_P, _I, _I, _I, _I, _I, _F, _I, C.c_uint32, _P, _P, _P, _P, _P],
-    "siu3r_panoptic_stage1": [_P] * 20 + [_I] * 9 + [_F, _F, _F, C.c_uint32, _P],
+    "siu3r_panoptic_stage1": [_P] * 20 + [_I] * 9 + [_F, _F, C.c_double, C.c_uint32, _P],
     "siu3r_panoptic_qcl": [_P, _P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P],
 }
 _RESTYPES = {"siu3r_last_error": C.c_char_p, "siu3r_raster_composite_feat_ws_bytes": C.c_int64, "siu3r_raster_pose_partial_rows": C.c_int64}

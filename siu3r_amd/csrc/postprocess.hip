@@ -178,7 +178,7 @@ __global__ __launch_bounds__(256) void pp_argmax_kernel(const float* p256, const
 __global__ void pp_accept_kernel(const int32_t* area, const int32_t* orig, const int32_t* kept_idx, const int32_t* n_keep,
                                  const int32_t* labels, const float* scores, int32_t* seg_id, int32_t* seg_label,
                                  int32_t* seg_fused, float* seg_score, int32_t* acc_list, int32_t* n_acc, int Q,
-                                 float overlap, uint32_t fuse_mask, int B) {
+                                 double overlap, uint32_t fuse_mask, int B) {
   const int b = blockIdx.x * blockDim.x + threadIdx.x;
   if (b >= B) return;
   const int nk = n_keep[b];
@@ -193,8 +193,10 @@ __global__ void pp_accept_kernel(const int32_t* area, const int32_t* orig, const
     const int a = area[b * Q + k], o = orig[b * Q + k];
     bool exists = a > 0 && o > 0;
     if (exists) {
+      // the reference divides two float32 tensors and compares the quotient's .item() -- a double -- with the double threshold
+      // (:1429-1433): at 0.8 a ratio that rounds to fp32(0.8) = 0.800000012 is ACCEPTED (4:5, 400:500, ...); a float32 comparison rejects it
       const float ratio = (float)a / (float)o;
-      if (!(ratio > overlap)) exists = false;
+      if (!((double)ratio > overlap)) exists = false;
     }
     if (!exists) continue;
     int sid_f;
@@ -285,7 +287,7 @@ extern "C" int siu3r_panoptic_stage1(const float* class_logits, const float* mas
                                      int32_t* seg_fused, float* seg_score, int32_t* acc_list, int32_t* n_acc,
                                      int32_t* seg, int32_t* sem, int32_t* ins, int B, int T, int Q, int C, int IH,
                                      int IW, int H, int W, int mask_size, float threshold, float mask_threshold,
-                                     float overlap, uint32_t fuse_mask, void* stream) {
+                                     double overlap, uint32_t fuse_mask, void* stream) {
   SIU3R_CHECK(class_logits && mask_logits_cl && probs && p256 && lab_map && seg, "panoptic_stage1: null pointer");
   SIU3R_CHECK(Q <= 128 && C <= 64, "panoptic_stage1: supports up to 128 queries / 64 classes (Q=%d C=%d)", Q, C);
   SIU3R_CHECK((int64_t)B * T * mask_size * mask_size * Q < 0x7fffffffll && (int64_t)T * H * W < 0x7fffffffll,

@@ -68,7 +68,8 @@ class VideoMask2FormerImageProcessor:
         check(_lib.lib().siu3r_panoptic_stage1(
             _p(class_logits), _p(mcl), _p(probs), _p(scores), _p(labels), _p(kept_idx), _p(n_keep_t), _p(p256), _p(lab_map),
             _p(area), _p(orig), _p(seg_id), _p(seg_label), _p(seg_fused), _p(seg_score), _p(acc_list), _p(n_acc), _p(seg),
-            _p(sem), _p(ins), B, T, Q, Cc, IH, IW, H, W, MASK_SIZE, threshold, mask_threshold, overlap_mask_area_threshold,
+            _p(sem), _p(ins), B, T, Q, Cc, IH, IW, H, W, MASK_SIZE, threshold, mask_threshold,
+            float(overlap_mask_area_threshold),  # a double, unrounded: the reference compares the float32 area ratio's .item() with it
             fuse_mask, _stream()))
         # one device->host read of the small tables (the reference does a .item() per query instead), asynchronous into pinned memory
         # (pinned staging buffer per host_slot: results that are pending at the same time -- SIU3RModel.forward_async -- must not share one)

@@ -94,4 +94,4 @@ def test_the_binding_declares_the_new_entry_point():
     sig = _lib.SIGNATURES["siu3r_raster_composite_rgb_bwd_abs"]
     plain = _lib.SIGNATURES["siu3r_raster_composite_rgb_bwd"]
     assert sig[:-1] == plain and sig[-2] == sig[-1] == plain[-1], "the plain call's arguments, then abs_mean2d in front of the stream"
-    assert _lib.ABI_VERSION == 12
+    assert _lib.ABI_VERSION == 13

@@ -223,7 +223,7 @@ def test_new_symbols_are_declared_exported_and_documented():
     assert len(_lib.SIGNATURES["siu3r_raster_project_aa"]) == len(_lib.SIGNATURES["siu3r_raster_project"]) + 1
     assert len(_lib.SIGNATURES["siu3r_raster_project_c2w_aa"]) == len(_lib.SIGNATURES["siu3r_raster_project_c2w"]) + 1
     assert _lib.SIGNATURES["siu3r_raster_project_bwd_aa"] == _lib.SIGNATURES["siu3r_raster_project_bwd"]
-    assert l.siu3r_mip_filter3d_ws.restype is _lib.C.c_int64 and l.siu3r_mip_filter3d_ws(3) >= 4 * (16 * 3 + 1) and l.siu3r_abi_version() == 12
+    assert l.siu3r_mip_filter3d_ws.restype is _lib.C.c_int64 and l.siu3r_mip_filter3d_ws(3) >= 4 * (16 * 3 + 1) and l.siu3r_abi_version() == 13
 
 
 def test_front_end_keywords_exist_and_default_off():

@@ -125,7 +125,7 @@ def test_new_symbols_are_declared_exported_and_signed():
     l = _lib.lib()
     for s in SYMBOLS:
         assert s in declared and hasattr(l, s) and s in _lib.SIGNATURES, s
-    assert l.siu3r_abi_version() == _lib.ABI_VERSION == 12
+    assert l.siu3r_abi_version() == _lib.ABI_VERSION == 13
     assert l.siu3r_bilagrid_tv_ws(6, 8, 16, 16) == 8 * 576  # 6 x 12 x 8 x 16 x 16 elements, 256 per workgroup
     assert l.siu3r_bilagrid_tv_ws(1, 2, 2, 2) == 8 and l.siu3r_bilagrid_tv_ws(64, 16, 64, 64) == 8 * 1024
     for bad in ((0, 8, 16, 16), (1, 1, 16, 16), (1, 17, 16, 16), (1, 8, 1, 16), (1, 8, 16, 1025)):

@@ -24,7 +24,7 @@ def test_new_symbols_are_declared_exported_and_signed():
         assert s in declared, f"{s} is not declared in include/siu3r_hip.h"
         assert hasattr(l, s), f"{s} is not exported"
         assert s in _lib.SIGNATURES, f"{s} has no ctypes signature"
-    assert l.siu3r_abi_version() == _lib.ABI_VERSION == 12
+    assert l.siu3r_abi_version() == _lib.ABI_VERSION == 13
     # the size query is a host function: 12 doubles per workgroup of 2,048 pixels
     assert l.siu3r_exposure_ws(6, 512, 512) == 6 * 128 * 12 * 8
     assert l.siu3r_exposure_ws(1, 1, 1) == 96 and l.siu3r_exposure_ws(2, 3, 683) == 2 * 2 * 96

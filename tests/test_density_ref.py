@@ -158,5 +158,5 @@ def test_header_and_ctypes_declare_the_density_entry_points():
     for s in ("siu3r_density_accumulate", "siu3r_density_plan_ws", "siu3r_density_plan", "siu3r_density_apply"):
         assert re.search(r"\b" + s + r"\s*\(", text), s
         assert s in _lib.SIGNATURES and hasattr(_lib.lib(), s)
-    assert re.search(r"#define\s+SIU3R_ABI_VERSION\s+12\b", text) and _lib.ABI_VERSION == 12
+    assert re.search(r"#define\s+SIU3R_ABI_VERSION\s+13\b", text) and _lib.ABI_VERSION == 13
     assert int(_lib.lib().siu3r_density_plan_ws(100003)) >= (100003 + 255) // 256

@@ -94,7 +94,7 @@ def test_entry_points_are_declared_and_exported():
         assert re.search(rf"\b{name}\s*\(", text), f"{name} is not declared in include/siu3r_hip.h"
         assert name in _lib.SIGNATURES and hasattr(l, name)
     assert len(_lib.SIGNATURES["siu3r_depth_loss"]) == 17 and l.siu3r_depth_loss_ws.restype is C.c_int64
-    assert l.siu3r_abi_version() == _lib.ABI_VERSION == 12
+    assert l.siu3r_abi_version() == _lib.ABI_VERSION == 13
     # host function: one record of 11 doubles per 1,024 pixels of a view plus 4 doubles per view
     assert l.siu3r_depth_loss_ws(1, 16, 64) == (11 + 4) * 8
     assert l.siu3r_depth_loss_ws(1, 5, 205) == (2 * 11 + 4) * 8
